@@ -10,7 +10,16 @@ runs data-parallel: each rank sweeps its own 75k-candidate shard (weak
 scaling) and the per-shard top-k is all-gathered over RCCL/xGMI, so the
 whole job evaluates N x 75k candidates per suggest.
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print one JSON result line. --dump-outputs DIR also
+writes what the last timed step returned (DIR/suggestions.npy), so two
+builds can be compared output for output: the inputs are seeded and
+identical from run to run. --full is where measurements beyond the
+headline figure belong; today there are none, the other configurations
+(--full-refit, --fp64) being timed paths of their own.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 """
 
 import argparse
@@ -62,6 +71,16 @@ def trial_from(params: dict, uid: int) -> vz.Trial:
   return t
 
 
+def dump_outputs(out_dir: str, suggestions) -> None:
+  """Writes what a caller of the timed suggest() received, as .npy."""
+  os.makedirs(out_dir, exist_ok=True)
+  # (count, DIM) float64: suggested parameter values, columns x0..x{DIM-1}.
+  values = np.array(
+      [[s.parameters.get_value(f'x{i}') for i in range(DIM)]
+       for s in suggestions], dtype=np.float64)
+  np.save(os.path.join(out_dir, 'suggestions.npy'), values)
+
+
 def main() -> None:
   parser = argparse.ArgumentParser()
   parser.add_argument('--gpus', type=int, default=1)
@@ -75,7 +94,15 @@ def main() -> None:
                       help='float64 end-to-end (the reference forces '
                            'jax x64); HIP fp32 kernels are bypassed '
                            'for rocBLAS DGEMM paths')
+  parser.add_argument('--dump-outputs', metavar='DIR', default=None,
+                      help='after the timed steps, write the last timed '
+                           "step's suggestions to DIR/suggestions.npy")
+  parser.add_argument('--full', action='store_true',
+                      help='also run the measurements beyond the '
+                           'headline figure (none at present)')
   args = parser.parse_args()
+  if args.steps < 1:
+    parser.error('--steps must be at least 1')
 
   world_size = int(os.environ.get('WORLD_SIZE', '1'))
   rank = int(os.environ.get('RANK', '0'))
@@ -121,7 +148,7 @@ def main() -> None:
   designer.update(CompletedTrials(trials), ActiveTrials())
   next_uid = N_TRIALS + 1
 
-  def one_step(uid: int) -> None:
+  def one_step(uid: int):
     # A step = one full suggest (GP refit + 75k-eval sweep) and the
     # completion of its trial, so every timed step does the whole
     # pipeline at N ~ 1000.
@@ -129,6 +156,7 @@ def main() -> None:
     params = dict(suggestions[0].parameters.as_dict())
     designer.update(CompletedTrials([trial_from(params, uid)]),
                     ActiveTrials())
+    return suggestions
 
   for w in range(args.warmup):
     one_step(next_uid)
@@ -137,7 +165,7 @@ def main() -> None:
   sync()
   t0 = time.perf_counter()
   for k in range(args.steps):
-    one_step(next_uid)
+    last_suggestions = one_step(next_uid)
     next_uid += 1
   sync()
   elapsed = time.perf_counter() - t0
@@ -148,6 +176,9 @@ def main() -> None:
                      device=device if use_gpu else 'cpu')
     torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
+
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last_suggestions)
 
   ms_per_step = elapsed / args.steps * 1000.0
   value = ms_per_step

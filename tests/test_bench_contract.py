@@ -62,3 +62,38 @@ def test_fp64_flag_reports_dtype(tiny_bench, monkeypatch, capsys):
   d = _run(tiny_bench, monkeypatch, capsys,
            ['--steps', '1', '--warmup', '0', '--fp64'])
   assert d['dtype'] == 'fp64'
+
+
+def test_steps_sets_the_number_of_timed_steps(tiny_bench, monkeypatch,
+                                              capsys):
+  calls = []
+  real = tiny_bench.VizierGPBandit.suggest
+
+  def counting(self, count=None):
+    calls.append(count)
+    return real(self, count)
+  monkeypatch.setattr(tiny_bench.VizierGPBandit, 'suggest', counting)
+  d = _run(tiny_bench, monkeypatch, capsys,
+           ['--steps', '2', '--warmup', '1'])
+  assert d['steps'] == 2 and d['warmup'] == 1
+  assert len(calls) == 3  # warmup + timed, nothing else
+
+
+def test_dump_outputs_writes_last_suggestion(tiny_bench, monkeypatch,
+                                             capsys, tmp_path):
+  import numpy as np
+  out = tmp_path / 'dump'
+  d = _run(tiny_bench, monkeypatch, capsys,
+           ['--steps', '1', '--warmup', '0', '--dump-outputs', str(out)])
+  assert d['ms_per_step'] > 0
+  assert [p.name for p in out.iterdir()] == ['suggestions.npy']
+  values = np.load(out / 'suggestions.npy')
+  assert values.shape == (1, 20) and values.dtype == np.float64
+  assert np.all((values >= -5.0) & (values <= 5.0))
+
+
+def test_full_flag_keeps_the_result_line(tiny_bench, monkeypatch, capsys):
+  d = _run(tiny_bench, monkeypatch, capsys,
+           ['--steps', '1', '--warmup', '0', '--full'])
+  assert d['metric'] == 'suggest_wall_clock_ms_gp_bandit_20d_n1000'
+  assert d['value'] == d['ms_per_step'] > 0

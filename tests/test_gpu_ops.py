@@ -1,10 +1,27 @@
 """GPU tests: HIP kernels vs the fp32 torch reference (run via gpurun)."""
 
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+
+def posterior_training_data(n=200, d=10, seed=0):
+  """Training set of TestPosteriorScoreKernel (seeded, CPU)."""
+  g = torch.Generator().manual_seed(seed)
+  x = torch.rand(n, d, generator=g)
+  # Real observation noise keeps the fitted noise (and cond(K)) in a
+  # regime where the fp32 K_inv quadform is accurate, so the kernel
+  # numerics test can be TIGHT. The near-noiseless/degenerate regime
+  # is exercised end-to-end by the designer + regret evidence.
+  y = torch.sin(3 * x[:, 0]) + x[:, 1] + 0.1 * torch.randn(n, generator=g)
+  return x, y
 
 
 @pytest.fixture(scope='module')
@@ -85,17 +102,21 @@ class TestGramKernel:
 
 class TestPosteriorScoreKernel:
 
-  def _posterior(self, n=200, d=10, seed=0):
+  def _posterior(self):
+    # The hyperparameters are one stored train_gp(num_restarts=2,
+    # max_iters=20, seed=0) fit of this data: the fp32 L-BFGS fit lands
+    # in a different local optimum depending on the CPU's thread count
+    # and reduction order (amplitude 0.40 .. 0.54 seen), and the
+    # tolerances below are statements about the kernels at ONE
+    # posterior, not about the fit. The fp64 posterior cache is rebuilt
+    # from them here.
     from vizier_amd._src.gp import gp_model
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(n, d, generator=g)
-    # Real observation noise keeps the fitted noise (and cond(K)) in a
-    # regime where the fp32 K_inv quadform is accurate, so the kernel
-    # numerics test can be TIGHT. The near-noiseless/degenerate regime
-    # is exercised end-to-end by the designer + regret evidence.
-    y = torch.sin(3 * x[:, 0]) + x[:, 1] +         0.1 * torch.randn(n, generator=g)
-    post = gp_model.train_gp(x, y, num_restarts=2, max_iters=20, seed=seed)
-    return post
+    x, y = posterior_training_data()
+    with open(os.path.join(_GOLDEN, 'gp_posterior_n200_d10.json')) as f:
+      fit = json.load(f)
+    raw = torch.tensor(fit['raw'], dtype=torch.float32)
+    return gp_model._build_posterior_cache(
+        x, y, raw, fit['nll'], precompute_inverse=True)
 
   def _to_cuda(self, post):
     from vizier_amd._src.gp.gp_model import GPParams, GPPosterior
@@ -216,7 +237,8 @@ class TestPosteriorScoreKernel:
     # bf16 rounds z = x/ls to 8 mantissa bits; the d^2 error passes
     # through the kernel and is AMPLIFIED by the variance cancellation
     # amp^2 - k^T K_inv k near training points, so score deviations
-    # reach ~7% of amp at this shape (measured 0.026 on amp 0.38).
+    # reach ~10% of amp at this shape (0.038 on amp 0.40 at the stored
+    # fit, from a CPU emulation of the same rounding).
     # The tight rounding-exactness check against the torch bf16 oracle
     # is the next test; here we bound the drift vs full fp32.
     assert torch.allclose(got16, got32, atol=0.12 * amp)

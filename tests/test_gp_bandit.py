@@ -314,3 +314,17 @@ class TestEnsembleDesigners:
     assert hasattr(score_fn, 'scoring')
     assert hasattr(score_fn, 'codec_identity')
     assert not getattr(score_fn, 'graph_safe', True) is False
+
+  def test_qei_set_scorer_is_not_offered_for_graph_capture(self):
+    # qEI over candidate sets factors a batched covariance (rocSOLVER
+    # cholesky), which refuses stream capture; a capture attempt that
+    # fails leaves the process unable to use the GPU afterwards, so the
+    # optimizer must go straight to the eager loop.
+    d = VizierGPBandit(self._problem(), GPBanditConfig(
+        max_evaluations=200, ard_restarts=2, ard_max_iters=5,
+        acquisition='qei'))
+    d.update(CompletedTrials(self._trials(10)), ActiveTrials())
+    d._fit()
+    score_fn, q = d._score_factory(4)
+    assert q == 4
+    assert score_fn.graph_safe is False

@@ -512,9 +512,13 @@ class VizierGPBandit(Designer, Predictor):
         if trust_region is not None:
           scores = trust_region.apply(dense[:, 0, :], scores)
         return scores
-      # Capture-eligible (the optimizer auto-falls-back if the batched
-      # cholesky refuses capture on this build).
-      score_fn.graph_safe = True
+      # Not capture-eligible: qei_mc_scores factors the joint covariance
+      # with the rocSOLVER batched cholesky, which refuses stream capture
+      # (same as the UCB-PE set scorer). Attempting the capture and
+      # falling back is not harmless: the invalidated capture leaves the
+      # process's stream and generator in capture mode, and every later
+      # GPU call in the process fails.
+      score_fn.graph_safe = False
       return score_fn, count
 
     if cfg.acquisition == 'ei':

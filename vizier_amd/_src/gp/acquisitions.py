@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -393,6 +393,25 @@ class Fp8GramCache:
                                      self.amp, self.scale)
 
 
+def bf16_train_operands(x: torch.Tensor, lengthscales: torch.Tensor
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+  """Training-side operands of the fused bf16 scorer, built once per suggest.
+
+  Returns (z2b, n2): z2b (N, Dp) = bf16(x / lengthscales), zero-padded to
+  a multiple of 32 columns, and n2 (N,) = fp32 row norms of the ROUNDED
+  values (the layout ext.posterior_scores_bf16 consumes).
+  """
+  with torch.no_grad():
+    z = x / lengthscales
+    d = z.shape[1]
+    dp = (d + 31) // 32 * 32
+    z2b = torch.zeros(z.shape[0], dp, dtype=torch.bfloat16,
+                      device=z.device)
+    z2b[:, :d] = z.to(torch.bfloat16)
+    n2 = (z2b.float() ** 2).sum(-1)
+  return z2b, n2
+
+
 def qei_mc_scores(mean: torch.Tensor, cov: torch.Tensor,
                   eps: torch.Tensor, best_value: float) -> torch.Tensor:
   """Monte-Carlo qEI over candidate SETS with common random numbers.
@@ -464,15 +483,8 @@ class ScoringFunction:
                                      float(posterior.params.amplitude))
     if (gram_dtype == 'bf16' and posterior.x.is_cuda and
         posterior.K_inv is not None and self._acq_name is not None):
-      with torch.no_grad():
-        z = posterior.x / posterior.params.lengthscales
-        d = z.shape[1]
-        dp = (d + 31) // 32 * 32
-        z2b = torch.zeros(z.shape[0], dp, dtype=torch.bfloat16,
-                          device=z.device)
-        z2b[:, :d] = z.to(torch.bfloat16)
-        n2 = (z2b.float() ** 2).sum(-1)
-      self._bf16_cache = (z2b, n2)
+      self._bf16_cache = bf16_train_operands(
+          posterior.x, posterior.params.lengthscales)
     if trust_region is not None:
       self._onehot_u8 = trust_region._onehot.to(torch.uint8)
       self._tr_radius = float(trust_region.trust_radius)

@@ -174,6 +174,41 @@ hipStream_t current_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
 }
 
+// Host-side argument checks shared by the fused scorer bindings. The
+// kernels index x, alpha, kinv and onehot by (n, d) taken from xq/x
+// alone, so every other operand must agree BEFORE anything is launched.
+void check_scorer_args(const torch::Tensor& xq, const torch::Tensor& x,
+                       const torch::Tensor& lengthscales,
+                       const torch::Tensor& alpha,
+                       const torch::Tensor& kinv,
+                       const torch::Tensor& onehot) {
+  TORCH_CHECK(xq.dim() == 2 && x.dim() == 2, "xq and x must be 2-D");
+  const int64_t d = xq.size(1), n = x.size(0);
+  TORCH_CHECK(x.size(1) == d, "x must have xq's ", d, " columns, got ",
+              x.size(1));
+  TORCH_CHECK(lengthscales.numel() == d, "lengthscales must have ", d,
+              " elements, got ", lengthscales.numel());
+  TORCH_CHECK(alpha.numel() == n, "alpha must have ", n,
+              " elements, got ", alpha.numel());
+  TORCH_CHECK(kinv.dim() == 2 && kinv.size(0) == n && kinv.size(1) == n,
+              "kinv must be (", n, ", ", n, ")");
+  TORCH_CHECK(onehot.scalar_type() == torch::kUInt8 && onehot.is_cuda(),
+              "onehot must be a uint8 GPU tensor");
+  TORCH_CHECK(onehot.numel() == d, "onehot must have ", d,
+              " elements, got ", onehot.numel());
+}
+
+// Cached training-side operands (z2b / z2q rows, n2) of the bf16/fp8
+// scorers must cover the same n training rows as x.
+void check_cached_operands(const torch::Tensor& z2, const torch::Tensor& n2,
+                           const torch::Tensor& x, const char* name) {
+  TORCH_CHECK(z2.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(z2.dim() == 2 && z2.size(0) == x.size(0), name,
+              " must have x's ", x.size(0), " rows");
+  TORCH_CHECK(n2.numel() == x.size(0), "n2 must have ", x.size(0),
+              " elements, got ", n2.numel());
+}
+
 torch::Tensor gram_matern52(torch::Tensor x1, torch::Tensor x2,
                             torch::Tensor lengthscales, double amplitude) {
   x1 = check_f32(x1, "x1");
@@ -448,6 +483,7 @@ torch::Tensor posterior_scores_chunked(
   lengthscales = check_f32(lengthscales, "lengthscales");
   alpha = check_f32(alpha, "alpha");
   kinv = check_f32(kinv, "kinv");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
   onehot = onehot.contiguous();
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   TORCH_CHECK(d <= 512, "posterior_scores supports D <= 512");
@@ -535,11 +571,14 @@ torch::Tensor posterior_scores_bf16(
   kinv = check_f32(kinv, "kinv");
   TORCH_CHECK(z2b.scalar_type() == torch::kBFloat16 && z2b.is_cuda(),
               "z2b must be bf16 cuda");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
+  check_cached_operands(z2b, n2, x, "z2b");
   z2b = z2b.contiguous();
   onehot = onehot.contiguous();
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   const int dp = z2b.size(1);
   TORCH_CHECK(dp % 32 == 0 && dp <= 512, "dp must be mult of 32, <=512");
+  TORCH_CHECK(dp >= d, "z2b must have at least ", d, " columns");
   auto inv_ls = 1.0f / lengthscales;
   auto k_ws = torch::empty({b, n}, xq.options());
   auto mu_ws = torch::empty({b}, xq.options());
@@ -599,6 +638,7 @@ std::vector<torch::Tensor> posterior_mean_std(
   lengthscales = check_f32(lengthscales, "lengthscales");
   alpha = check_f32(alpha, "alpha");
   kinv = check_f32(kinv, "kinv");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
   onehot = onehot.contiguous();
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   TORCH_CHECK(d <= 512, "posterior_mean_std supports D <= 512");
@@ -673,11 +713,14 @@ std::vector<torch::Tensor> posterior_mean_std_fp8(
   kinv = check_f32(kinv, "kinv");
   TORCH_CHECK(z2q.scalar_type() == torch::kFloat8_e4m3fn,
               "z2q must be float8_e4m3fn");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
+  check_cached_operands(z2q, n2, x, "z2q");
   z2q = z2q.contiguous();
   onehot = onehot.contiguous();
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   const int dp = z2q.size(1);
   TORCH_CHECK(dp % 32 == 0 && dp <= 512, "dp must be mult of 32, <=512");
+  TORCH_CHECK(dp >= d, "z2q must have at least ", d, " columns");
   // Candidate side: quantize + dequantize with torch (tiny, no sync).
   auto z1 = xq / lengthscales;
   auto z1q = torch::zeros({b, dp},
@@ -725,15 +768,21 @@ torch::Tensor hv_scalarize_tr(
   const int m = means.size(0), b = means.size(1);
   const int s = weights.size(0);
   TORCH_CHECK(weights.size(1) == m, "weights/means metric mismatch");
+  TORCH_CHECK(sds.sizes() == means.sizes(),
+              "sds must have the shape of means");
   torch::Tensor ref_t, dist_t;
   const float* ref_p = nullptr;
   const float* dist_p = nullptr;
   if (ref.has_value()) {
     ref_t = check_f32(*ref, "ref");
+    TORCH_CHECK(ref_t.numel() == m, "ref must have ", m,
+                " elements, got ", ref_t.numel());
     ref_p = ref_t.data_ptr<float>();
   }
   if (dist.has_value()) {
     dist_t = check_f32(*dist, "dist");
+    TORCH_CHECK(dist_t.numel() == b, "dist must have ", b,
+                " elements, got ", dist_t.numel());
     dist_p = dist_t.data_ptr<float>();
   }
   auto out = torch::empty({b}, means.options());

@@ -121,10 +121,15 @@ class VectorizedEagleStrategy:
       self._cat_sizes_t = torch.tensor(self.categorical_sizes,
                                        device=self.device)
     # The fused HIP path replaces the ~30-launch torch step with 2 launches.
-    # The eagle kernels are fp32; fp64 sweeps (--fp64 parity mode) run
-    # the torch path on rocBLAS DGEMMs instead.
-    if self.device.type == 'cuda' and dtype == torch.float32:
-      from vizier_amd._src.ops import dispatch as ops
+    # fp64 sweeps (--fp64 parity mode) run the torch path on rocBLAS
+    # DGEMMs unless VIZIER_AMD_FP64_HIP=1 selects the fp64 kernels
+    # (eagle_step_f64.hip; opt-in because their RNG stream differs from
+    # the torch one). The flag is read here, at construction.
+    from vizier_amd._src.ops import dispatch as ops
+    self._f64_hip = (self.device.type == 'cuda' and
+                     dtype == torch.float64 and ops.fp64_hip_enabled())
+    if (self.device.type == 'cuda' and dtype == torch.float32) or \
+        self._f64_hip:
       self._ext = ops.require_ext()
       # [0:2] device iteration counters; [2:10] megakernel per-phase
       # cycle accumulators (A, barA, B, barB, B2, barB2, C, barC) —
@@ -254,7 +259,9 @@ class VectorizedEagleStrategy:
       cat_factor = (cfg.pure_categorical_perturbation_factor
                     if self.n_continuous == 0
                     else cfg.categorical_perturbation_factor)
-      out_cont, out_cat = self._ext.eagle_suggest(
+      suggest_kernel = (self._ext.eagle_suggest_f64 if self._f64_hip
+                        else self._ext.eagle_suggest)
+      out_cont, out_cat = suggest_kernel(
           state.continuous, state.categorical, state.rewards,
           state.perturbations, self._cat_sizes_long, self._iter_t,
           n_batches, self.batch_size, cfg.visibility, cfg.gravity,
@@ -369,7 +376,9 @@ class VectorizedEagleStrategy:
     elif self._ext is not None:
       # The kernel updates best_reward and the device iteration counter
       # in place (graph-capturable: no host-varying arguments).
-      self._ext.eagle_update(
+      update_kernel = (self._ext.eagle_update_f64 if self._f64_hip
+                       else self._ext.eagle_update)
+      update_kernel(
           state.continuous, state.categorical, state.rewards,
           state.perturbations, batch.continuous.contiguous(),
           batch.categorical.contiguous(), batch_rewards.contiguous(),

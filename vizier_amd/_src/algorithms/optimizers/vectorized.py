@@ -134,6 +134,10 @@ class VectorizedOptimizer:
       return False
     if strategy.categorical_sizes or strategy.n_parallel != 1:
       return False
+    if strategy.dtype != torch.float32:
+      # The megakernel is fp32 only; an fp64 strategy on the fp64 HIP
+      # kernels (VIZIER_AMD_FP64_HIP=1) takes the hipGraph path.
+      return False
     post = scoring.posterior
     return (scoring._acq_name is not None and scoring._tr_anchored and
             getattr(scoring, 'gram_dtype', 'fp32') == 'fp32' and

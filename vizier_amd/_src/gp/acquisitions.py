@@ -499,16 +499,55 @@ class ScoringFunction:
   def _can_fuse(self, xs: torch.Tensor) -> bool:
     """True when the GPU K^-1 quadform path applies (any acquisition).
 
-    The HIP scorer kernels are fp32; fp64 parity mode scores through
-    the torch predict path (rocBLAS DGEMM / fp64 matrix cores).
+    fp32 always; float64 (parity mode) only with VIZIER_AMD_FP64_HIP=1,
+    otherwise it scores through the torch predict path (rocBLAS DGEMM).
     """
-    return (xs.is_cuda and xs.dtype == torch.float32 and
-            self.posterior.K_inv is not None)
+    if self.posterior.K_inv is None or not xs.is_cuda:
+      return False
+    if xs.dtype == torch.float32:
+      return True
+    from vizier_amd._src.ops import dispatch as ops
+    return ops.use_fp64_hip(xs) and ops.use_fp64_hip(self.posterior.x)
+
+  def _call_fp64_hip(self, xs: torch.Tensor) -> torch.Tensor:
+    """float64 on the GPU with VIZIER_AMD_FP64_HIP=1 (see _can_fuse)."""
+    post = self.posterior
+    from vizier_amd._src.ops import dispatch as ops
+    if (self._acq_name is not None and self._tr_anchored and
+        self.gram_dtype == 'fp32'):
+      # The 3-kernel fp64 scorer (posterior_score_f64.hip): k-vectors,
+      # K^-1 quadform on the fp64 matrix cores, finalize. No host sync,
+      # so the sweep captures it in a hipGraph like the fp32 scorer.
+      onehot = self._onehot_u8
+      if onehot is None:
+        onehot = torch.zeros(xs.shape[-1], dtype=torch.uint8,
+                             device=xs.device)
+        self._onehot_u8 = onehot
+      ext = ops.require_ext()
+      return ext.posterior_scores_f64(
+          xs, post.x, post.params.lengthscales, self._amp, self._mean_c,
+          post.alpha, post.K_inv, onehot, ops.ACQ_CODES[self._acq_name],
+          self._coef, self._best,
+          self._tr_radius if self.trust_region is not None else 0.0)
+    # Composed path (exotic acquisition, unanchored trust region, or a
+    # low-precision gram_dtype, which has no fp64 form): fp64 HIP Gram
+    # for the k-vectors + rocBLAS DGEMM for the quadform.
+    k = ops.gram_matern52(xs, post.x, post.params.lengthscales,
+                          post.params.amplitude)
+    amp2 = self._amp * self._amp
+    var = (amp2 - (k * (k @ post.K_inv)).sum(-1)).clamp_min(1e-12)
+    mean = self._mean_c + k @ post.alpha
+    scores = self.acquisition(mean, var.sqrt())
+    if self.trust_region is not None:
+      scores = self.trust_region.apply(xs, scores)
+    return scores
 
   def __call__(self, xs: torch.Tensor) -> torch.Tensor:
     if self._can_fuse(xs):
       post = self.posterior
       from vizier_amd._src.ops import dispatch as ops
+      if xs.dtype == torch.float64:
+        return self._call_fp64_hip(xs)
       if (self._acq_name is not None and self._tr_anchored and
           self._bf16_cache is not None):
         # bf16 fused scorer: cached training operands, 3 launches.

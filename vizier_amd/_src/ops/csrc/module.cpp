@@ -162,6 +162,41 @@ extern "C" void launch_eagle_update(
     float base_perturbation, unsigned long long seed,
     hipStream_t stream);
 
+// fp64 parity-mode kernels (posterior_score_f64.hip, gram_matern52_f64.hip,
+// eagle_step_f64.hip).
+extern "C" void ps_f64_quadform_shape(int n, int* ctiles, int* slabs,
+                                      int* slab_rows);
+
+extern "C" void launch_posterior_score_f64(
+    const double* xq, const double* x, const double* inv_ls,
+    const double* alpha, const double* kinv, const unsigned char* onehot,
+    double* k_ws, double* mu_ws, double* dist_ws, double* part,
+    double* out, double* mean_out, double* sd_out, int b, int n, int d,
+    double amp2, double mean_c, int acq, double coef, double best_value,
+    double tr_radius, hipStream_t stream);
+
+extern "C" void launch_gram_matern52_f64(
+    const double* x1, const double* x2, const double* inv_ls, double* out,
+    int n, int m, int d, double amp2, int sym, hipStream_t stream);
+
+extern "C" void launch_eagle_suggest_f64(
+    const double* pool_cont, const long* pool_cat, const double* rewards,
+    const double* perturbations, const long* cat_sizes, double* out_cont,
+    long* out_cat, const unsigned long long* iter_ptr, int n_batches,
+    int batch_size, int pool_size, int q, int dc, int dcat, int max_cat,
+    double visibility, double gravity, double neg_gravity,
+    double norm_scale, double cat_factor, double p_same,
+    unsigned long long seed, hipStream_t stream);
+
+extern "C" void launch_eagle_update_f64(
+    double* pool_cont, long* pool_cat, double* rewards,
+    double* perturbations, const double* batch_cont, const long* batch_cat,
+    const double* batch_rewards, const long* cat_sizes,
+    double* best_reward, unsigned long long* iter_ptr, int n_batches,
+    int batch_size, int q, int dc, int dcat, double penalize_factor,
+    double perturbation_lower_bound, double base_perturbation,
+    unsigned long long seed, hipStream_t stream);
+
 namespace {
 
 torch::Tensor check_f32(const torch::Tensor& t, const char* name) {
@@ -987,10 +1022,241 @@ int64_t eagle_sweep(
   return ret;
 }
 
+// -- fp64 parity-mode bindings -------------------------------------------------
+
+torch::Tensor check_f64(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat64, name, " must be fp64");
+  return t.contiguous();
+}
+
+// Tensors the Eagle kernels update in place: never copied.
+void check_inplace(const torch::Tensor& t, torch::ScalarType dtype,
+                   const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype &&
+              t.is_contiguous(), name,
+              " must be a contiguous GPU tensor of the kernel's dtype");
+}
+
+// Runs the three fp64 scorer kernels on the current stream. `want_score`
+// selects the (B,) acquisition score; otherwise mean and sd are written.
+// Returns {score} or {mean, sd, dist}. No host sync: capturable.
+std::vector<torch::Tensor> posterior_f64_impl(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot, bool want_score, int64_t acq,
+    double coef, double best_value, double tr_radius) {
+  xq = check_f64(xq, "xq");
+  x = check_f64(x, "x");
+  lengthscales = check_f64(lengthscales, "lengthscales");
+  alpha = check_f64(alpha, "alpha");
+  kinv = check_f64(kinv, "kinv");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
+  onehot = onehot.contiguous();
+  const int b = xq.size(0), d = xq.size(1), n = x.size(0);
+  TORCH_CHECK(d <= 512, "posterior_scores_f64 supports D <= 512");
+  TORCH_CHECK(b >= 1 && n >= 1, "posterior_scores_f64 needs B, N >= 1");
+  TORCH_CHECK(acq >= 0 && acq <= 5, "unknown acquisition code ", acq);
+  auto inv_ls = lengthscales.reciprocal();
+  int ctiles = 0, slabs = 0, slab_rows = 0;
+  ps_f64_quadform_shape(n, &ctiles, &slabs, &slab_rows);
+  auto k_ws = torch::empty({b, n}, xq.options());
+  auto mu_ws = torch::empty({b}, xq.options());
+  auto dist_ws = torch::empty({b}, xq.options());
+  auto part = torch::empty({b, (int64_t)ctiles * slabs}, xq.options());
+  torch::Tensor out, mean, sd;
+  double* out_p = nullptr;
+  double* mean_p = nullptr;
+  double* sd_p = nullptr;
+  if (want_score) {
+    out = torch::empty({b}, xq.options());
+    out_p = out.data_ptr<double>();
+  } else {
+    mean = torch::empty({b}, xq.options());
+    sd = torch::empty({b}, xq.options());
+    mean_p = mean.data_ptr<double>();
+    sd_p = sd.data_ptr<double>();
+  }
+  launch_posterior_score_f64(
+      xq.data_ptr<double>(), x.data_ptr<double>(),
+      inv_ls.data_ptr<double>(), alpha.data_ptr<double>(),
+      kinv.data_ptr<double>(), onehot.data_ptr<unsigned char>(),
+      k_ws.data_ptr<double>(), mu_ws.data_ptr<double>(),
+      dist_ws.data_ptr<double>(), part.data_ptr<double>(), out_p, mean_p,
+      sd_p, b, n, d, amplitude * amplitude, mean_c, (int)acq, coef,
+      best_value, tr_radius, current_stream());
+  if (want_score) return {out};
+  return {mean, sd, dist_ws};
+}
+
+torch::Tensor posterior_scores_f64(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot, int64_t acq, double coef,
+    double best_value, double tr_radius) {
+  return posterior_f64_impl(xq, x, lengthscales, amplitude, mean_c, alpha,
+                            kinv, onehot, true, acq, coef, best_value,
+                            tr_radius)[0];
+}
+
+std::vector<torch::Tensor> posterior_mean_std_f64(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot) {
+  return posterior_f64_impl(xq, x, lengthscales, amplitude, mean_c, alpha,
+                            kinv, onehot, false, 4, 0.0, 0.0, 0.0);
+}
+
+torch::Tensor gram_matern52_f64(torch::Tensor x1, torch::Tensor x2,
+                                torch::Tensor lengthscales,
+                                double amplitude) {
+  x1 = check_f64(x1, "x1");
+  x2 = check_f64(x2, "x2");
+  lengthscales = check_f64(lengthscales, "lengthscales");
+  TORCH_CHECK(x1.dim() == 2 && x2.dim() == 2, "x1 and x2 must be 2-D");
+  const int n = x1.size(0), m = x2.size(0), d = x1.size(1);
+  TORCH_CHECK(x2.size(1) == d && lengthscales.numel() == d,
+              "dimension mismatch");
+  auto out = torch::empty({n, m}, x1.options());
+  if (n == 0 || m == 0) return out;
+  auto inv_ls = lengthscales.reciprocal();
+  const int sym = (x1.data_ptr() == x2.data_ptr() && n == m) ? 1 : 0;
+  launch_gram_matern52_f64(x1.data_ptr<double>(), x2.data_ptr<double>(),
+                           inv_ls.data_ptr<double>(),
+                           out.data_ptr<double>(), n, m, d,
+                           amplitude * amplitude, sym, current_stream());
+  return out;
+}
+
+std::vector<torch::Tensor> eagle_suggest_f64(
+    torch::Tensor pool_cont, torch::Tensor pool_cat, torch::Tensor rewards,
+    torch::Tensor perturbations, torch::Tensor cat_sizes,
+    torch::Tensor iter_counter, int64_t n_batches, int64_t batch_size,
+    double visibility, double gravity, double neg_gravity,
+    double norm_scale, double cat_factor, double p_same, int64_t seed,
+    torch::Tensor out_cont, torch::Tensor out_cat, int64_t max_cat) {
+  pool_cont = check_f64(pool_cont, "pool_cont");
+  rewards = check_f64(rewards, "rewards");
+  perturbations = check_f64(perturbations, "perturbations");
+  TORCH_CHECK(iter_counter.scalar_type() == torch::kInt64 &&
+              iter_counter.is_cuda() && iter_counter.is_contiguous() &&
+              iter_counter.numel() >= 2,
+              "iter_counter must be int64 cuda with >= 2 slots");
+  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3,
+              "pool_cont / pool_cat must be (P, q, D*)");
+  TORCH_CHECK(pool_cat.is_cuda() &&
+              pool_cat.scalar_type() == torch::kInt64 &&
+              cat_sizes.is_cuda() &&
+              cat_sizes.scalar_type() == torch::kInt64,
+              "pool_cat / cat_sizes must be int64 GPU tensors");
+  pool_cat = pool_cat.contiguous();
+  cat_sizes = cat_sizes.contiguous();
+  const int pool_size = pool_cont.size(0);
+  const int q = pool_cont.size(1);
+  const int dc = pool_cont.size(2);
+  const int dcat = pool_cat.size(2);
+  // The kernel keeps scale[MAX_POOL] in LDS and indexes the pool by
+  // batch_start + b < n_batches * batch_size.
+  TORCH_CHECK(pool_size >= 1 && pool_size <= 128,
+              "eagle_suggest_f64 supports 1 <= pool <= 128");
+  TORCH_CHECK(q >= 1 && q <= 16, "eagle_suggest_f64 supports q <= 16");
+  TORCH_CHECK(batch_size >= 1 && n_batches >= 1 &&
+              n_batches * batch_size <= pool_size,
+              "n_batches * batch_size must not exceed the pool");
+  TORCH_CHECK(pool_cat.size(0) == pool_size && pool_cat.size(1) == q &&
+              rewards.numel() == pool_size &&
+              perturbations.numel() == pool_size &&
+              cat_sizes.numel() == dcat, "pool shape mismatch");
+  check_inplace(out_cont, torch::kFloat64, "out_cont");
+  check_inplace(out_cat, torch::kInt64, "out_cat");
+  TORCH_CHECK(out_cont.numel() == batch_size * q * dc &&
+              out_cat.numel() == batch_size * q * dcat,
+              "out_cont / out_cat must be (batch, q, D*)");
+  TORCH_CHECK(dcat == 0 || max_cat >= 1, "max_cat must be >= 1");
+  launch_eagle_suggest_f64(
+      pool_cont.data_ptr<double>(),
+      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
+      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      out_cont.data_ptr<double>(),
+      dcat ? out_cat.data_ptr<long>() : nullptr,
+      (const unsigned long long*)iter_counter.data_ptr<int64_t>(),
+      (int)n_batches, (int)batch_size, pool_size, q, dc, dcat,
+      (int)max_cat, visibility, gravity, neg_gravity, norm_scale,
+      cat_factor, p_same, (unsigned long long)seed, current_stream());
+  return {out_cont, out_cat};
+}
+
+void eagle_update_f64(torch::Tensor pool_cont, torch::Tensor pool_cat,
+                      torch::Tensor rewards, torch::Tensor perturbations,
+                      torch::Tensor batch_cont, torch::Tensor batch_cat,
+                      torch::Tensor batch_rewards, torch::Tensor cat_sizes,
+                      torch::Tensor best_reward, torch::Tensor iter_counter,
+                      int64_t n_batches, double penalize_factor,
+                      double perturbation_lower_bound,
+                      double base_perturbation, int64_t seed) {
+  check_inplace(pool_cont, torch::kFloat64, "pool_cont");
+  check_inplace(pool_cat, torch::kInt64, "pool_cat");
+  check_inplace(rewards, torch::kFloat64, "rewards");
+  check_inplace(perturbations, torch::kFloat64, "perturbations");
+  check_inplace(best_reward, torch::kFloat64, "best_reward");
+  check_inplace(iter_counter, torch::kInt64, "iter_counter");
+  batch_cont = check_f64(batch_cont, "batch_cont");
+  batch_rewards = check_f64(batch_rewards, "batch_rewards");
+  TORCH_CHECK(batch_cat.is_cuda() &&
+              batch_cat.scalar_type() == torch::kInt64 &&
+              cat_sizes.is_cuda() &&
+              cat_sizes.scalar_type() == torch::kInt64,
+              "batch_cat / cat_sizes must be int64 GPU tensors");
+  batch_cat = batch_cat.contiguous();
+  cat_sizes = cat_sizes.contiguous();
+  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3 &&
+              batch_cont.dim() == 3 && batch_cat.dim() == 3,
+              "pool / batch tensors must be (rows, q, D*)");
+  const int pool_size = pool_cont.size(0);
+  const int batch_size = batch_cont.size(0);
+  const int q = batch_cont.size(1);
+  const int dc = batch_cont.size(2);
+  const int dcat = batch_cat.size(2);
+  TORCH_CHECK(batch_size >= 1 && n_batches >= 1 &&
+              n_batches * batch_size <= pool_size,
+              "n_batches * batch_size must not exceed the pool");
+  TORCH_CHECK(pool_cont.size(1) == q && pool_cont.size(2) == dc &&
+              pool_cat.size(0) == pool_size && pool_cat.size(1) == q &&
+              pool_cat.size(2) == dcat && batch_cat.size(0) == batch_size &&
+              batch_cat.size(1) == q && rewards.numel() == pool_size &&
+              perturbations.numel() == pool_size &&
+              batch_rewards.numel() == batch_size &&
+              cat_sizes.numel() == dcat && best_reward.numel() >= 1 &&
+              iter_counter.numel() >= 2, "pool / batch shape mismatch");
+  launch_eagle_update_f64(
+      pool_cont.data_ptr<double>(),
+      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
+      batch_cont.data_ptr<double>(),
+      dcat ? batch_cat.data_ptr<long>() : nullptr,
+      batch_rewards.data_ptr<double>(),
+      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      best_reward.data_ptr<double>(),
+      (unsigned long long*)iter_counter.data_ptr<int64_t>(),
+      (int)n_batches, batch_size, q, dc, dcat, penalize_factor,
+      perturbation_lower_bound, base_perturbation,
+      (unsigned long long)seed, current_stream());
+}
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("posterior_scores_f64", &posterior_scores_f64,
+        "fp64 fused GP posterior scorer, MFMA f64 quadform (gfx950)");
+  m.def("posterior_mean_std_f64", &posterior_mean_std_f64,
+        "fp64 fused (mean, sd, dist) over candidates (gfx950)");
+  m.def("gram_matern52_f64", &gram_matern52_f64,
+        "fp64 difference-form Matern-5/2 Gram / cross-Gram (gfx950)");
+  m.def("eagle_suggest_f64", &eagle_suggest_f64,
+        "fp64 fused Eagle suggest step (gfx950)");
+  m.def("eagle_update_f64", &eagle_update_f64,
+        "fp64 fused Eagle update step (gfx950)");
   m.def("gram_matern52_batched", &gram_matern52_batched,
         "Batched-restart fused Matern-5/2 gram (+noise*I, optional "
         "gradient factor)");

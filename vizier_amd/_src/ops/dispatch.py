@@ -9,6 +9,7 @@ for the kernels, compared in tests/test_gpu_ops.py).
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -47,6 +48,22 @@ def require_ext():
   return ext
 
 
+def fp64_hip_enabled() -> bool:
+  """True iff VIZIER_AMD_FP64_HIP=1: float64 GPU tensors take the fp64 HIP
+  kernels (posterior_score_f64 / gram_matern52_f64 / eagle_step_f64).
+
+  Opt-in, default off: the fp64 Eagle kernels draw a different RNG stream
+  than the torch fp64 path, so suggestions change when it is switched on.
+  Read from the environment at every call (never cached).
+  """
+  return os.environ.get('VIZIER_AMD_FP64_HIP') == '1'
+
+
+def use_fp64_hip(t: torch.Tensor) -> bool:
+  """The fp64 kernel path applies to `t`: flag on, float64, on the GPU."""
+  return t.is_cuda and t.dtype == torch.float64 and fp64_hip_enabled()
+
+
 def gram_matern52(x1: torch.Tensor, x2: Optional[torch.Tensor],
                   lengthscales: torch.Tensor,
                   amplitude: torch.Tensor) -> torch.Tensor:
@@ -56,6 +73,17 @@ def gram_matern52(x1: torch.Tensor, x2: Optional[torch.Tensor],
     x2t = x1 if x2 is None else x2
     return ext.gram_matern52(x1.contiguous(), x2t.contiguous(),
                              lengthscales.contiguous(), float(amplitude))
+  if (x1.dim() == 2 and use_fp64_hip(x1) and
+      (x2 is None or (x2.dim() == 2 and use_fp64_hip(x2))) and
+      not any(getattr(t, 'requires_grad', False)
+              for t in (x1, x2, lengthscales, amplitude))):
+    # fp64 parity mode, prediction time only: the kernel has no backward,
+    # so anything autograd tracks (the fit) stays on the torch formula.
+    ext = require_ext()
+    x1c = x1.contiguous()
+    x2c = x1c if x2 is None else x2.contiguous()
+    return ext.gram_matern52_f64(x1c, x2c, lengthscales.contiguous(),
+                                 float(amplitude))
   return _torch_matern.gram_matern52(x1, x2, lengthscales, amplitude)
 
 

@@ -92,3 +92,180 @@ def test_splitmix64_oracle_known_values():
   # The uniform keeps the top 24 bits: ((h >> 40) + 0.5) / 2^24.
   h = int(oracle.splitmix64(7 ^ int(oracle.splitmix64(3 ^ 5))))
   assert float(oracle.uniform(7, 3, 5)) == ((h >> 40) + 0.5) / 2.0**24
+
+
+def test_float32_uniform_reproduces_the_kernel_rounding():
+  # vz_rng_uniform is (float(k) + 0.5f) * 2^-24f with k = h >> 40. For
+  # (seed 7, offset 3), by hand from splitmix64:
+  #   idx 5: k = 0x2b40f7 < 2^23, so k + 0.5 is exact: the fp64 value.
+  #   idx 0: k = 0xe880a9 >= 2^23 and odd: the tie k + 0.5 rounds to the
+  #          even neighbour k + 1 = 0xe880aa.
+  #   idx 6: k = 0x8ea526 >= 2^23 and even: the tie rounds down to k.
+  #   idx 848669: k = 2^24 - 1, the tie rounds up to 2^24: exactly 1.0.
+  def k_of(idx):
+    return int(oracle.splitmix64(7 ^ int(oracle.splitmix64(3 ^ idx)))) >> 40
+  assert [k_of(i) for i in (5, 0, 6, 848669)] == [
+      0x2b40f7, 0xe880a9, 0x8ea526, 2**24 - 1]
+  got = oracle.uniform(7, 3, [5, 0, 6, 848669], np.float32)
+  assert got.dtype == np.float32
+  assert [float(v).hex() for v in got] == [
+      '0x1.5a07bc0000000p-3', '0x1.d101540000000p-1',
+      '0x1.1d4a4c0000000p-1', '0x1.0000000000000p+0']
+  # The fp64 stream keeps the half: it differs wherever k >= 2^23.
+  wide = oracle.uniform(7, 3, [5, 0, 6, 848669])
+  assert [float(v).hex() for v in wide] == [
+      '0x1.5a07bc0000000p-3', '0x1.d101530000000p-1',
+      '0x1.1d4a4d0000000p-1', '0x1.ffffff0000000p-1']
+  # The kernels tolerate the endpoint 1.0f: the Laplace draw clamps, and
+  # the refill takes min(int(u * size), size - 1).
+  lap = oracle.laplace(7, 3, 848669, np.float32)
+  assert np.isfinite(lap) and float(lap) == -np.log1p(
+      -2.0 * float(np.float32(0.499999)))
+
+
+def _legacy_suggest_q1(pool_cont, pool_cat, rewards, perts, cat_sizes,
+                       offset, n_batches, batch_size, seed, cfg):
+  """The q = 1 float64 oracle as it stood before it was generalised to
+  q >= 1 and to float32, kept to pin its results bit for bit."""
+  import math
+  pool_size, _, dc = pool_cont.shape
+  dcat = pool_cat.shape[2]
+  max_cat = int(max(cat_sizes)) if dcat else 0
+  flat = pool_cont.reshape(pool_size, dc)
+  cats = pool_cat.reshape(pool_size, dcat)
+  start = (offset % n_batches) * batch_size
+  out_cont = np.empty((batch_size, 1, dc))
+  out_cat = np.empty((batch_size, 1, dcat), dtype=np.int64)
+
+  def unif(off, idx):
+    idx = np.asarray(idx, dtype=np.uint32).astype(np.uint64)
+    h = oracle.splitmix64(np.uint64(seed) ^
+                          oracle.splitmix64(np.uint64(off) ^ idx))
+    return ((h >> np.uint64(40)).astype(np.float64) + 0.5) / 16777216.0
+
+  def lap(off, idx):
+    u = unif(off, idx) - 0.5
+    a = np.minimum(np.abs(u), 0.499999)
+    return np.where(u >= 0.0, -1.0, 1.0) * np.log1p(-2.0 * a)
+
+  for b in range(batch_size):
+    me = start + b
+    diff = flat[me][None, :] - flat
+    d2 = (diff * diff).sum(-1) + (cats != cats[me][None, :]).sum(-1)
+    with np.errstate(invalid='ignore'):
+      direction = np.where(rewards - rewards[me] >= 0.0, cfg.gravity,
+                           -cfg.negative_gravity)
+    force = np.exp(-cfg.visibility * d2 / (dc + dcat) * 10.0)
+    s = np.where(np.isfinite(rewards), direction * force, 0.0)
+    n_pull = max(float((s > 0).sum()), 1.0)
+    n_push = max(float((s < 0).sum()), 1.0)
+    scale = cfg.normalization_scale * np.where(
+        s > 0, s * (1.0 / n_pull), s * (1.0 / n_push))
+    scale_sum = scale.sum()
+    moved = flat[me] + (scale @ flat - flat[me] * scale_sum)
+    sign = np.where(lap(offset, b * dc + np.arange(dc)) >= 0.0, 1.0, -1.0)
+    out_cont[b, 0] = moved + sign * perts[me]
+    for jd in range(dcat):
+      size = int(cat_sizes[jd])
+      logit_same = math.log(cfg.p_same)
+      logit_diff = math.log((1.0 - cfg.p_same) / max(size - 1.0, 1e-9))
+      pert_noise = float(lap(offset ^ oracle.TAG_CAT_NOISE,
+                             b * dcat + jd)) * cfg.cat_factor * perts[me]
+      c = np.arange(size)
+      logits = np.array([scale[cats[:, jd] == cc].sum() for cc in c])
+      logits = logits + logit_diff
+      logits[int(cats[me, jd])] += -scale_sum + logit_same - logit_diff
+      logits = logits + pert_noise
+      u = unif(offset ^ oracle.TAG_GUMBEL, (b * dcat + jd) * max_cat + c)
+      vals = logits + -np.log(-np.log(np.maximum(u, 1e-20)))
+      out_cat[b, 0, jd] = int(np.argmax(vals))
+  return out_cont, out_cat
+
+
+def test_generalised_oracle_keeps_the_q1_float64_results():
+  cfg = oracle.Config()
+  for pool, batch, dc, cat_sizes in ((50, 25, 3, [3, 5]), (30, 10, 4, []),
+                                     (20, 10, 0, [1, 6])):
+    inputs = oracle.steady_pool(pool, 1, dc, cat_sizes, seed=pool)
+    args = (*inputs, cat_sizes, 5, pool // batch, batch, 2024, cfg)
+    want_cont, want_cat = _legacy_suggest_q1(*args)
+    got_cont, got_cat, _ = oracle.suggest(*args)
+    assert got_cont.dtype == np.float64
+    assert np.array_equal(got_cont, want_cont)
+    assert np.array_equal(got_cat, want_cat)
+
+
+def test_oracle_update_refills_whole_q_rows():
+  # q = 3: a dead row is refilled over all q * Dc features from the
+  # uniforms at me * q * Dc + j, categories from me * q * Dcat + j with
+  # the size of dimension j % Dcat. float32 and float64 draw the same k.
+  cfg = oracle.Config()
+  pool, batch, q, dc, cat_sizes = 20, 10, 3, 2, [3, 5]
+  cont, cat, rewards, perts = oracle.steady_pool(pool, q, dc, cat_sizes, seed=4)
+  rewards[:] = 0.0
+  perts[10] = 8e-5                     # one penalty away from dead
+  batch_cont, batch_cat = cont[:batch] + 1.0, cat[:batch]
+  batch_rewards = np.full(batch, -1.0)
+  batch_rewards[3] = 2.0               # row 13 improves, the new best
+  for dtype in (np.float64, np.float32):
+    out = oracle.update(cont, cat, rewards, perts, batch_cont, batch_cat,
+                        batch_rewards, cat_sizes, 1.0, 5, 2, 77, cfg, dtype)
+    assert out[0].dtype == dtype and out[2].dtype == dtype
+    assert out[5][0] == 'dead' and out[5][3] == 'improved'
+    assert set(out[5][1:3] + out[5][4:]) == {'penalised'}
+    assert out[4] == 2.0
+    want = oracle.uniform(77, 5 ^ oracle.TAG_REFILL_CONT,
+                          10 * q * dc + np.arange(q * dc), dtype)
+    assert np.array_equal(out[0][10].reshape(-1), want)
+    u = oracle.uniform(77, 5 ^ oracle.TAG_REFILL_CAT,
+                       10 * q * 2 + np.arange(q * 2), np.float64)
+    sizes = np.tile(cat_sizes, q)
+    assert np.array_equal(out[1][10].reshape(-1),
+                          np.minimum((u * sizes).astype(np.int64),
+                                     sizes - 1))
+    assert np.array_equal(out[0][13], batch_cont[3].astype(dtype))
+    assert out[2][10] == -np.inf and out[3][10] == dtype(cfg.perturbation)
+    assert out[3][11] == dtype(perts[11]) * dtype(cfg.penalize_factor)
+
+
+def test_oracle_q3_noise_is_normalised_over_q():
+  # With a lone firefly the move is zero, so out - pool is noise * pert:
+  # per continuous dimension its max-abs over the q axis is exactly pert.
+  cfg = oracle.Config()
+  cont, cat, rewards, perts = oracle.steady_pool(10, 3, 4, [], seed=2)
+  rewards[:] = -np.inf                 # no forces at all
+  out, _, _ = oracle.suggest(cont, cat, rewards, perts, [], 7, 2, 5, 11,
+                             cfg)
+  start = (7 % 2) * 5
+  step = np.abs(out - cont[start:start + 5])
+  assert np.allclose(step.max(axis=1), perts[start:start + 5, None],
+                     rtol=1e-12)
+  assert (step.min(axis=1) < perts[start:start + 5, None]).any()
+
+
+def test_oracle_q3_move_matches_the_torch_strategy():
+  # With zero perturbation the suggestion is the deterministic move:
+  # eagle.py::_mutate (float64, CPU) and the oracle agree at q = 3, so
+  # distances over q * D, n_features = Dc + Dcat and the pull / push
+  # normalisation are the strategy's.
+  s = eagle_lib.VectorizedEagleStrategy(
+      n_continuous=4, categorical_sizes=[3, 5], batch_size=5, n_parallel=3,
+      seed=1, device='cpu', dtype=torch.float64)
+  state = s.init_state()
+  n_batches = s.pool_size // s.batch_size
+  g = torch.Generator().manual_seed(0)
+  state.rewards = torch.randn(s.pool_size, generator=g, dtype=torch.float64)
+  state.rewards[2] = -float('inf')
+  state.iterations = n_batches + 2
+  state.perturbations.zero_()
+  want = s.suggest(state).continuous.numpy()
+  c = s.config
+  got, _, _ = oracle.suggest(
+      state.continuous.numpy(), state.categorical.numpy(),
+      state.rewards.numpy(), np.zeros(s.pool_size), [3, 5],
+      state.iterations, n_batches, s.batch_size, 1,
+      oracle.Config(visibility=c.visibility, gravity=c.gravity,
+                    negative_gravity=c.negative_gravity,
+                    normalization_scale=c.normalization_scale))
+  assert got.shape == want.shape == (5, 3, 4)
+  assert float(np.abs(got - want).max()) < 1e-13

@@ -3,7 +3,8 @@
   posterior_score_f64.hip  ps_kvec_f64 + ps_quadform_f64 (MFMA f64 16x16x4,
                            slabs, candidate tiles) + ps_finalize_f64
   gram_matern52_f64.hip    difference-form Gram / cross-Gram
-  eagle_step_f64.hip       suggest / update against tests/eagle_f64_oracle.py
+  eagle_step_f64.hip       suggest / update against tests/eagle_f64_oracle.py,
+                           at q = 1 and at q > 1
 
 Scorer operands are the fp32-valued cases of tests/scorer_cases.py, so
 `.double()` is exact and `reference(case)` is the exact-operand reference.
@@ -245,27 +246,19 @@ def test_gram_dispatch_under_flag(ext, monkeypatch):
 # -- eagle --------------------------------------------------------------------------
 
 
-def _eagle_inputs(pool, dc, cat_sizes, seed):
+def _eagle_inputs(pool, dc, cat_sizes, seed, q=1):
   """A steady-state pool: a few -inf rewards, spread perturbations."""
-  rng = np.random.default_rng(seed)
-  pool_cont = rng.random((pool, 1, dc))
-  pool_cat = np.stack([rng.integers(0, s, size=(pool, 1))
-                       for s in cat_sizes], axis=-1).astype(np.int64) \
-      if cat_sizes else np.zeros((pool, 1, 0), dtype=np.int64)
-  rewards = rng.normal(size=pool)
-  rewards[rng.choice(pool, 3, replace=False)] = -np.inf
-  perts = 0.16 * 0.7 ** rng.integers(0, 6, size=pool)
-  return pool_cont, pool_cat, rewards, perts
+  return oracle.steady_pool(pool, q, dc, cat_sizes, seed)
 
 
 def _run_suggest(ext, pool_cont, pool_cat, rewards, perts, cat_sizes,
                  offset, n_batches, batch, seed, cfg):
   dev = 'cuda'
-  dc, dcat = pool_cont.shape[2], pool_cat.shape[2]
+  q, dc, dcat = pool_cont.shape[1], pool_cont.shape[2], pool_cat.shape[2]
   iter_t = torch.zeros(12, dtype=torch.long, device=dev)
   iter_t[:2] = offset
-  out_cont = torch.empty(batch, 1, dc, dtype=torch.float64, device=dev)
-  out_cat = torch.empty(batch, 1, dcat, dtype=torch.long, device=dev)
+  out_cont = torch.empty(batch, q, dc, dtype=torch.float64, device=dev)
+  out_cat = torch.empty(batch, q, dcat, dtype=torch.long, device=dev)
   ext.eagle_suggest_f64(
       torch.from_numpy(pool_cont).to(dev), torch.from_numpy(pool_cat).to(dev),
       torch.from_numpy(rewards).to(dev), torch.from_numpy(perts).to(dev),
@@ -294,12 +287,12 @@ def test_eagle_suggest_continuous(ext, pool, batch, dc):
   assert err <= tol
 
 
-def test_eagle_suggest_mixed(ext):
+def _check_suggest_mixed(ext, q):
   cfg = oracle.Config()
   pool, batch, dc, cat_sizes = 50, 25, 3, [3, 5]
   seed, n_batches = 2024, 2
   offset = 5
-  inputs = _eagle_inputs(pool, dc, cat_sizes, seed=77)
+  inputs = _eagle_inputs(pool, dc, cat_sizes, seed=77, q=q)
   want_cont, want_cat, margin = oracle.suggest(
       *inputs, cat_sizes, offset, n_batches, batch, seed, cfg)
   # Every top-2 `logit + gumbel` gap is far above rounding: the argmax is
@@ -316,7 +309,41 @@ def test_eagle_suggest_mixed(ext):
   assert 0.0 < changed < 1.0
 
 
+def test_eagle_suggest_mixed(ext):
+  _check_suggest_mixed(ext, q=1)
+
+
+def test_eagle_suggest_mixed_q3(ext):
+  # q > 1 (what acquisition='qei' runs): distances over the flat q * D
+  # features, noise normalised over the q axis, draws indexed over q.
+  _check_suggest_mixed(ext, q=3)
+
+
+def test_eagle_suggest_continuous_q2(ext):
+  cfg = oracle.Config()
+  pool, batch, dc, seed, n_batches = 60, 20, 5, 12345, 3
+  offset = 8                            # batch_start = 40
+  inputs = _eagle_inputs(pool, dc, [], seed=pool + dc, q=2)
+  want, _, _ = oracle.suggest(*inputs, [], offset, n_batches, batch, seed,
+                              cfg)
+  got, _ = _run_suggest(ext, *inputs, [], offset, n_batches, batch, seed,
+                        cfg)
+  tol = 8.0 * pool * U * (1.0 + float(np.abs(inputs[0]).max()))
+  err = float(np.abs(got - want).max())
+  print(f'OBSERVED suggest q2 {(pool, batch, dc)}: {err:.3e} '
+        f'(bound {tol:.3e})')
+  assert got.shape == (batch, 2, dc) and err <= tol
+
+
 def test_eagle_update_bitwise(ext):
+  _check_update_bitwise(ext, q=1)
+
+
+def test_eagle_update_bitwise_q3(ext):
+  _check_update_bitwise(ext, q=3)
+
+
+def _check_update_bitwise(ext, q):
   cfg = oracle.Config()
   pool, batch, dc, cat_sizes = 50, 25, 3, [3, 5]
   strategy_seed, n_batches, offset = 99, 2, 5
@@ -324,10 +351,10 @@ def test_eagle_update_bitwise(ext):
   start = (offset % n_batches) * batch
   rng = np.random.default_rng(8)
   pool_cont, pool_cat, rewards, perts = _eagle_inputs(pool, dc, cat_sizes,
-                                                      seed=9)
+                                                      seed=9, q=q)
   rewards[start:start + batch] = rng.normal(size=batch)
-  batch_cont = rng.random((batch, 1, dc))
-  batch_cat = np.stack([rng.integers(0, s, size=(batch, 1))
+  batch_cont = rng.random((batch, q, dc))
+  batch_cat = np.stack([rng.integers(0, s, size=(batch, q))
                         for s in cat_sizes], axis=-1).astype(np.int64)
   # Even rows improve, odd rows do not; rows 1 and 3 are one penalty away
   # from the lower bound (dead), row 4 improves but is already below it
@@ -364,8 +391,8 @@ def test_eagle_update_bitwise(ext):
     assert np.array_equal(got.cpu().numpy(), expect)
   assert float(best_t[0]) == want[4]
   assert iter_t[:2].tolist() == [offset + 1, offset]
-  # The refilled rows hold the widened 24-bit uniforms.
-  refilled = t[0][start + 1, 0].cpu().numpy() * 2.0 ** 24 - 0.5
+  # The refilled rows hold the widened 24-bit uniforms, over all q.
+  refilled = t[0][start + 1].cpu().numpy() * 2.0 ** 24 - 0.5
   assert np.array_equal(refilled, np.round(refilled))
 
 

@@ -471,10 +471,29 @@ class TestEagleKernels:
     out_g = gpu.suggest(state_g)
     err = (out_c.continuous - out_g.continuous.cpu()).abs().max()
     assert float(err) < 1e-4, f'move mismatch {err}'
-    # With zero perturbation, categorical sampling is near-deterministic
-    # only at p_same=0.98; just require the same dtype/shape and validity.
+    # The categories are the NumPy oracle's (tests/eagle_f64_oracle.py:
+    # the kernel's RNG bit for bit, formulas in float64), wherever its
+    # top-2 `logit + gumbel` margin exceeds tau = 4 x the
+    # float32-vs-float64 difference of that sum; every entry does.
+    import eagle_f64_oracle as oracle
     assert out_g.categorical.shape == out_c.categorical.shape
-    assert int(out_g.categorical.max()) < 3
+    c = gpu.config
+    args = (state_c.continuous.numpy(), state_c.categorical.numpy(),
+            rewards.numpy(), np.zeros(cpu.pool_size, dtype=np.float32), [3],
+            n_init, n_init, cpu.batch_size, 3,
+            oracle.Config(
+                visibility=c.visibility, gravity=c.gravity,
+                negative_gravity=c.negative_gravity,
+                normalization_scale=c.normalization_scale,
+                cat_factor=c.categorical_perturbation_factor,
+                p_same=c.prob_same_category_without_perturbation))
+    _, want_cat, margin, vals64 = oracle.suggest(
+        *args, dtype=np.float32, arith=np.float64, return_vals=True)
+    vals32 = oracle.suggest(*args, dtype=np.float32, arith=np.float32,
+                            return_vals=True)[3]
+    tau = 4.0 * float(np.nanmax(np.abs(vals32 - vals64)))
+    assert margin > tau, (margin, tau)
+    assert np.array_equal(out_g.categorical.cpu().numpy(), want_cat)
 
   def test_update_accept_reject(self, ext):
     from vizier_amd._src.algorithms.optimizers import eagle as eagle_lib

@@ -73,6 +73,11 @@ class EagleState:
   best_reward: torch.Tensor      # scalar
 
 
+# Limits of the fused HIP step kernels (eagle_step.hip, eagle_step_f64.hip).
+HIP_MAX_POOL = 128
+HIP_MAX_PARALLEL = 16
+
+
 def _laplace(shape, generator, device, dtype) -> torch.Tensor:
   u = torch.rand(shape, generator=generator, device=device,
                  dtype=dtype) - 0.5
@@ -128,8 +133,16 @@ class VectorizedEagleStrategy:
     from vizier_amd._src.ops import dispatch as ops
     self._f64_hip = (self.device.type == 'cuda' and
                      dtype == torch.float64 and ops.fp64_hip_enabled())
-    if (self.device.type == 'cuda' and dtype == torch.float32) or \
-        self._f64_hip:
+    # The step kernels keep the pool's forces in LDS (MAX_POOL = 128) and
+    # normalise noise over at most MAX_Q = 16 parallel candidates; a
+    # larger pool (e.g. max_pool_size 100 rounded up to a batch size of
+    # 48 -> 144, or config.pool_size > 128) runs the torch step.
+    fits_kernels = (self.pool_size <= HIP_MAX_POOL and
+                    n_parallel <= HIP_MAX_PARALLEL)
+    self._f64_hip = self._f64_hip and fits_kernels
+    if fits_kernels and (
+        (self.device.type == 'cuda' and dtype == torch.float32) or
+        self._f64_hip):
       self._ext = ops.require_ext()
       # [0:2] device iteration counters; [2:10] megakernel per-phase
       # cycle accumulators (A, barA, B, barB, B2, barB2, C, barC) —

@@ -198,9 +198,23 @@ batched_trsv_lower_kernel(const float* __restrict__ L,  // (R, N, N)
 // a (R x column-tiles) grid per panel — 2 launches per panel (~64
 // total) with the O(N^2) trailing work spread over the chip.
 
+// No workgroup reads a diagonal block that another workgroup of the same
+// launch writes. With one row tile (gridDim.y == 1) the only workgroup
+// of a matrix factors the block and writes it in place. With more, every
+// workgroup reads the UNFACTORED block, so workgroup y == 0 must not
+// overwrite it in this launch: a workgroup that starts late (R x rtiles
+// beyond what the chip holds at once; dispatch order is not a contract)
+// would factor the factored block and write a wrong L21 slice. When the
+// block was written in place, 2048 copies of a positive definite N = 321
+// matrix all came back with info = 289. It parks the factor in
+// `dscratch` (R, NB, NB) instead, and workgroup (r, 0) of this round's
+// trailing kernel, which never reads the diagonal block, copies it into
+// place. `dscratch` is null when the launch has one row tile.
+
 extern "C" __global__ __launch_bounds__(CB) void
 batched_potrf_panel_kernel(float* __restrict__ A, int* __restrict__ info,
-                           int r_count, int n, int k0) {
+                           float* __restrict__ dscratch, int r_count,
+                           int n, int k0) {
   __shared__ float diag[NB][NB + 1];
   __shared__ float rows_lds[CB][NB + 1];
   const int r = blockIdx.x;
@@ -259,9 +273,15 @@ batched_potrf_panel_kernel(float* __restrict__ A, int* __restrict__ info,
   }
   __syncthreads();
   if (blockIdx.y == 0) {
+    float* ds = dscratch ? dscratch + (long)r * NB * NB : nullptr;
     for (int e = tid; e < nb * nb; e += CB) {
       const int i = e / nb, c = e % nb;
-      M[(long)(k0 + i) * n + k0 + c] = (c <= i) ? diag[i][c] : 0.0f;
+      const float v = (c <= i) ? diag[i][c] : 0.0f;
+      if (ds) {
+        ds[e] = v;
+      } else {
+        M[(long)(k0 + i) * n + k0 + c] = v;
+      }
     }
   }
   const int tile_rows = has_rows ? min(CB, n - row0) : 0;
@@ -294,8 +314,9 @@ batched_potrf_panel_kernel(float* __restrict__ A, int* __restrict__ info,
 }
 
 extern "C" __global__ __launch_bounds__(CB) void
-batched_potrf_trailing_kernel(float* __restrict__ A, int r_count, int n,
-                              int k0) {
+batched_potrf_trailing_kernel(float* __restrict__ A,
+                              const float* __restrict__ dscratch,
+                              int r_count, int n, int k0) {
   __shared__ float jpanel[64][NB];
   __shared__ float rows_lds[CB][NB + 1];
   const int r = blockIdx.x;
@@ -303,6 +324,14 @@ batched_potrf_trailing_kernel(float* __restrict__ A, int r_count, int n,
   float* M = A + (long)r * n * n;
   const int tid = threadIdx.x;
   const int nb = min(NB, n - k0);
+  if (dscratch != nullptr && blockIdx.y == 0) {
+    // The factored diagonal block the panel kernel parked. Nothing in
+    // this launch reads rows k0 .. k0 + nb.
+    const float* ds = dscratch + (long)r * NB * NB;
+    for (int e = tid; e < nb * nb; e += CB) {
+      M[(long)(k0 + e / nb) * n + k0 + e % nb] = ds[e];
+    }
+  }
   const int jb = k0 + nb + blockIdx.y * 64;
   if (jb >= n) return;
   const int jl = min(64, n - jb);
@@ -1013,25 +1042,35 @@ extern "C" int launch_batched_potrf_v5(const float* A, float* panels,
   return 0;
 }
 
-extern "C" void launch_batched_potrf_v2(float* A, int* info, int r,
-                                        int n, hipStream_t stream) {
+// True iff some round of the v2 factorization of an n x n matrix runs
+// more than one row tile, i.e. needs the (R, NB, NB) diagonal scratch.
+extern "C" int batched_potrf_needs_scratch(int n) {
+  return n - NB > CB ? 1 : 0;
+}
+
+extern "C" void launch_batched_potrf_v2(float* A, int* info,
+                                        float* dscratch, int r, int n,
+                                        hipStream_t stream) {
   for (int k0 = 0; k0 < n; k0 += NB) {
     const int nb = (n - k0) < NB ? (n - k0) : NB;
     const int rows = n - (k0 + nb);
     const int rtiles = rows > 0 ? (rows + CB - 1) / CB : 1;
+    // rtiles > 1 implies rows > CB, so the trailing launch that moves
+    // the parked block into place always follows.
+    float* park = rtiles > 1 ? dscratch : nullptr;
     hipLaunchKernelGGL(batched_potrf_panel_kernel, dim3(r, rtiles),
-                       dim3(CB), 0, stream, A, info, r, n, k0);
+                       dim3(CB), 0, stream, A, info, park, r, n, k0);
     const int jtiles = (rows + 63) / 64;
     if (jtiles > 0) {
       hipLaunchKernelGGL(batched_potrf_trailing_kernel,
-                         dim3(r, jtiles), dim3(CB), 0, stream, A, r, n,
-                         k0);
+                         dim3(r, jtiles), dim3(CB), 0, stream, A,
+                         (const float*)park, r, n, k0);
     }
   }
 }
 
-extern "C" void launch_batched_potrf(float* A, int* info, int r, int n,
-                                     hipStream_t stream) {
+extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
+                                     int r, int n, hipStream_t stream) {
   // v4 measured SLOWER than v2 at the headline shape (3.63 vs 2.85 ms,
   // R=3 N=1000): the fused kernel's three inlined 32-wide solves blow
   // its register budget (VGPR 256 + 248 AGPRs, occupancy 1 wave/SIMD
@@ -1042,7 +1081,7 @@ extern "C" void launch_batched_potrf(float* A, int* info, int r, int n,
     use_v4 = (env != nullptr && env[0] == 'v' && env[1] == '4') ? 1 : 0;
   }
   if (!use_v4) {
-    launch_batched_potrf_v2(A, info, r, n, stream);
+    launch_batched_potrf_v2(A, info, dscratch, r, n, stream);
     return;
   }
   for (int k0 = 0; k0 < n; k0 += NB) {

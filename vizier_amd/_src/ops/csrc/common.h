@@ -73,8 +73,12 @@ __device__ __forceinline__ unsigned long long vz_splitmix64(
 __device__ __forceinline__ float vz_rng_uniform(unsigned long long seed,
                                                 unsigned long long offset,
                                                 unsigned int idx) {
+  // 24 bits k -> (k + 0.5) 2^-24 in (0, 1]. The sum is a float: exact
+  // for k < 2^23, rounded to even above (two k share a value), and
+  // k = 2^24 - 1 gives exactly 1.0f. Callers tolerate the endpoint: the
+  // Laplace draw clamps |u - 0.5|, the refill takes min(c, size - 1).
   unsigned long long h = vz_splitmix64(seed ^ vz_splitmix64(offset ^ idx));
-  return ((h >> 40) + 0.5f) * (1.0f / 16777216.0f);  // 24 bits -> (0,1)
+  return ((h >> 40) + 0.5f) * (1.0f / 16777216.0f);
 }
 
 __device__ __forceinline__ float vz_rng_laplace(unsigned long long seed,

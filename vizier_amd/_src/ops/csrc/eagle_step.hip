@@ -17,7 +17,7 @@
 #define MAX_POOL 128
 #define MAX_Q 16
 
-// -- counter-based RNG (splitmix64 -> uniform in (0,1)) ---------------------
+// -- counter-based RNG (splitmix64 -> uniform in (0,1], see common.h) -------
 
 #define splitmix64 vz_splitmix64
 #define rng_uniform vz_rng_uniform

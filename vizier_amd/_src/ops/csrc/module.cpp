@@ -116,8 +116,9 @@ extern "C" void launch_ps_quadform_finalize(
     float amp2, float mean_c, int acq, float coef, float best_value,
     float tr_radius, hipStream_t stream);
 
-extern "C" void launch_batched_potrf(float* A, int* info, int r, int n,
-                                     hipStream_t stream);
+extern "C" int batched_potrf_needs_scratch(int n);
+extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
+                                     int r, int n, hipStream_t stream);
 extern "C" int launch_batched_potrf_coop(float* A, int* info,
                                          unsigned int* bar, int r, int n,
                                          hipStream_t stream);
@@ -830,10 +831,17 @@ torch::Tensor hv_scalarize_tr(
 }
 
 std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
-  // (R, N, N) -> (L lower in a fresh tensor, info (R,) int32).
+  // (R, N, N) -> (L in a fresh tensor, info (R,) int32). Only the LOWER
+  // triangle of L is defined: the default path leaves K's values in the
+  // strict upper triangle outside the 32x32 diagonal blocks, and
+  // batched_trsv_lower never reads it. info[r] is the 1-based first
+  // column whose pivot is not > 0 (zero, negative or NaN), else 0.
   K = check_f32(K, "K");
   TORCH_CHECK(K.dim() == 3 && K.size(1) == K.size(2),
               "K must be (R, N, N)");
+  TORCH_CHECK(K.size(0) >= 1 && K.size(1) >= 1,
+              "batched_potrf needs R >= 1 and N >= 1, got R = ",
+              K.size(0), ", N = ", K.size(1));
   const int r = K.size(0), n = K.size(1);
   auto info = torch::zeros({r}, K.options().dtype(torch::kInt32));
   // Implementation ladder (VIZIER_AMD_CHOL_IMPL=v2|v3|v4|v5, default
@@ -884,8 +892,16 @@ std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
       return {L, info};
     }
   }
-  launch_batched_potrf(L.data_ptr<float>(), info.data_ptr<int>(), r, n,
-                       current_stream());
+  // Rounds with more than one row tile park their factored diagonal
+  // block here instead of overwriting what the other tiles still read.
+  torch::Tensor dscratch;
+  float* dscratch_p = nullptr;
+  if (batched_potrf_needs_scratch(n)) {
+    dscratch = torch::empty({r, 32, 32}, K.options());
+    dscratch_p = dscratch.data_ptr<float>();
+  }
+  launch_batched_potrf(L.data_ptr<float>(), info.data_ptr<int>(),
+                       dscratch_p, r, n, current_stream());
   return {L, info};
 }
 
@@ -895,11 +911,152 @@ torch::Tensor batched_trsv_lower(torch::Tensor L, torch::Tensor b) {
   TORCH_CHECK(L.dim() == 3 && L.size(1) == L.size(2) &&
               b.dim() == 2 && b.size(0) == L.size(0) &&
               b.size(1) == L.size(1), "shape mismatch");
+  TORCH_CHECK(L.size(0) >= 1 && L.size(1) >= 1,
+              "batched_trsv_lower needs R >= 1 and N >= 1, got R = ",
+              L.size(0), ", N = ", L.size(1));
   auto z = b.clone();
   launch_batched_trsv_lower(L.data_ptr<float>(), z.data_ptr<float>(),
                             (int)L.size(0), (int)L.size(1),
                             current_stream());
   return z;
+}
+
+// -- Eagle step bindings ------------------------------------------------------
+//
+// The fp32 (eagle_step.hip) and fp64 (eagle_step_f64.hip) kernels have
+// the same shape limits and index the same way, so the two pairs of
+// bindings share their argument checks. Every check throws before
+// anything is launched.
+
+torch::Tensor check_f64(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat64, name, " must be fp64");
+  return t.contiguous();
+}
+
+torch::Tensor check_real(const torch::Tensor& t, torch::ScalarType dtype,
+                         const char* name) {
+  return dtype == torch::kFloat64 ? check_f64(t, name) : check_f32(t, name);
+}
+
+// Tensors the Eagle kernels update in place: never copied.
+void check_inplace(const torch::Tensor& t, torch::ScalarType dtype,
+                   const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype &&
+              t.is_contiguous(), name,
+              " must be a contiguous GPU tensor of the kernel's dtype");
+}
+
+struct EagleShape {
+  int pool_size, batch_size, q, dc, dcat;
+};
+
+// Read-only operands are replaced by contiguous images; out_cont, out_cat
+// and iter_counter are written in place.
+EagleShape check_eagle_suggest_args(
+    torch::Tensor& pool_cont, torch::Tensor& pool_cat,
+    torch::Tensor& rewards, torch::Tensor& perturbations,
+    torch::Tensor& cat_sizes, const torch::Tensor& iter_counter,
+    int64_t n_batches, int64_t batch_size, const torch::Tensor& out_cont,
+    const torch::Tensor& out_cat, int64_t max_cat,
+    torch::ScalarType dtype) {
+  pool_cont = check_real(pool_cont, dtype, "pool_cont");
+  rewards = check_real(rewards, dtype, "rewards");
+  perturbations = check_real(perturbations, dtype, "perturbations");
+  TORCH_CHECK(iter_counter.scalar_type() == torch::kInt64 &&
+              iter_counter.is_cuda() && iter_counter.is_contiguous() &&
+              iter_counter.numel() >= 2,
+              "iter_counter must be int64 cuda with >= 2 slots");
+  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3,
+              "pool_cont / pool_cat must be (P, q, D*)");
+  TORCH_CHECK(pool_cat.is_cuda() &&
+              pool_cat.scalar_type() == torch::kInt64 &&
+              cat_sizes.is_cuda() &&
+              cat_sizes.scalar_type() == torch::kInt64,
+              "pool_cat / cat_sizes must be int64 GPU tensors");
+  pool_cat = pool_cat.contiguous();
+  cat_sizes = cat_sizes.contiguous();
+  EagleShape s;
+  s.pool_size = pool_cont.size(0);
+  s.batch_size = (int)batch_size;
+  s.q = pool_cont.size(1);
+  s.dc = pool_cont.size(2);
+  s.dcat = pool_cat.size(2);
+  // The kernel keeps scale[MAX_POOL = 128] in LDS, normalises noise
+  // over q <= MAX_Q = 16, and indexes the pool by batch_start + b <
+  // n_batches * batch_size.
+  TORCH_CHECK(pool_cont.size(0) >= 1 && pool_cont.size(0) <= 128,
+              "the Eagle step kernels support 1 <= pool <= 128, got ",
+              pool_cont.size(0));
+  TORCH_CHECK(s.q >= 1 && s.q <= 16,
+              "the Eagle step kernels support 1 <= q <= 16, got ", s.q);
+  TORCH_CHECK(batch_size >= 1 && n_batches >= 1 &&
+              n_batches * batch_size <= s.pool_size,
+              "n_batches * batch_size must not exceed the pool");
+  TORCH_CHECK(pool_cat.size(0) == s.pool_size && pool_cat.size(1) == s.q &&
+              rewards.numel() == s.pool_size &&
+              perturbations.numel() == s.pool_size &&
+              cat_sizes.numel() == s.dcat, "pool shape mismatch");
+  check_inplace(out_cont, dtype, "out_cont");
+  check_inplace(out_cat, torch::kInt64, "out_cat");
+  TORCH_CHECK(out_cont.numel() == batch_size * s.q * s.dc &&
+              out_cat.numel() == batch_size * s.q * s.dcat,
+              "out_cont / out_cat must be (batch, q, D*)");
+  TORCH_CHECK(s.dcat == 0 || max_cat >= 1, "max_cat must be >= 1");
+  return s;
+}
+
+// The pool, rewards, perturbations, best_reward and iter_counter are
+// updated in place; the batch operands are replaced by contiguous images.
+EagleShape check_eagle_update_args(
+    const torch::Tensor& pool_cont, const torch::Tensor& pool_cat,
+    const torch::Tensor& rewards, const torch::Tensor& perturbations,
+    torch::Tensor& batch_cont, torch::Tensor& batch_cat,
+    torch::Tensor& batch_rewards, torch::Tensor& cat_sizes,
+    const torch::Tensor& best_reward, const torch::Tensor& iter_counter,
+    int64_t n_batches, torch::ScalarType dtype) {
+  check_inplace(pool_cont, dtype, "pool_cont");
+  check_inplace(pool_cat, torch::kInt64, "pool_cat");
+  check_inplace(rewards, dtype, "rewards");
+  check_inplace(perturbations, dtype, "perturbations");
+  check_inplace(best_reward, dtype, "best_reward");
+  check_inplace(iter_counter, torch::kInt64, "iter_counter");
+  batch_cont = check_real(batch_cont, dtype, "batch_cont");
+  batch_rewards = check_real(batch_rewards, dtype, "batch_rewards");
+  TORCH_CHECK(batch_cat.is_cuda() &&
+              batch_cat.scalar_type() == torch::kInt64 &&
+              cat_sizes.is_cuda() &&
+              cat_sizes.scalar_type() == torch::kInt64,
+              "batch_cat / cat_sizes must be int64 GPU tensors");
+  batch_cat = batch_cat.contiguous();
+  cat_sizes = cat_sizes.contiguous();
+  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3 &&
+              batch_cont.dim() == 3 && batch_cat.dim() == 3,
+              "pool / batch tensors must be (rows, q, D*)");
+  EagleShape s;
+  s.pool_size = pool_cont.size(0);
+  s.batch_size = batch_cont.size(0);
+  s.q = batch_cont.size(1);
+  s.dc = batch_cont.size(2);
+  s.dcat = batch_cat.size(2);
+  TORCH_CHECK(pool_cont.size(0) >= 1 && pool_cont.size(0) <= 128,
+              "the Eagle step kernels support 1 <= pool <= 128, got ",
+              pool_cont.size(0));
+  TORCH_CHECK(s.q >= 1 && s.q <= 16,
+              "the Eagle step kernels support 1 <= q <= 16, got ", s.q);
+  TORCH_CHECK(s.batch_size >= 1 && n_batches >= 1 &&
+              n_batches * s.batch_size <= s.pool_size,
+              "n_batches * batch_size must not exceed the pool");
+  TORCH_CHECK(pool_cont.size(1) == s.q && pool_cont.size(2) == s.dc &&
+              pool_cat.size(0) == s.pool_size && pool_cat.size(1) == s.q &&
+              pool_cat.size(2) == s.dcat &&
+              batch_cat.size(0) == s.batch_size &&
+              batch_cat.size(1) == s.q && rewards.numel() == s.pool_size &&
+              perturbations.numel() == s.pool_size &&
+              batch_rewards.numel() == s.batch_size &&
+              cat_sizes.numel() == s.dcat && best_reward.numel() >= 1 &&
+              iter_counter.numel() >= 2, "pool / batch shape mismatch");
+  return s;
 }
 
 std::vector<torch::Tensor> eagle_suggest(
@@ -909,26 +1066,18 @@ std::vector<torch::Tensor> eagle_suggest(
     double visibility, double gravity, double neg_gravity,
     double norm_scale, double cat_factor, double p_same, int64_t seed,
     torch::Tensor out_cont, torch::Tensor out_cat, int64_t max_cat) {
-  pool_cont = check_f32(pool_cont, "pool_cont");
-  rewards = check_f32(rewards, "rewards");
-  perturbations = check_f32(perturbations, "perturbations");
-  TORCH_CHECK(iter_counter.scalar_type() == torch::kInt64 &&
-              iter_counter.is_cuda(), "iter_counter must be int64 cuda");
-  pool_cat = pool_cat.contiguous();
-  cat_sizes = cat_sizes.contiguous();
-  const int pool_size = pool_cont.size(0);
-  const int q = pool_cont.size(1);
-  const int dc = pool_cont.size(2);
-  const int dcat = pool_cat.size(2);
+  const EagleShape s = check_eagle_suggest_args(
+      pool_cont, pool_cat, rewards, perturbations, cat_sizes, iter_counter,
+      n_batches, batch_size, out_cont, out_cat, max_cat, torch::kFloat32);
   launch_eagle_suggest(
       pool_cont.data_ptr<float>(),
-      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
       rewards.data_ptr<float>(), perturbations.data_ptr<float>(),
-      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
       out_cont.data_ptr<float>(),
-      dcat ? out_cat.data_ptr<long>() : nullptr,
+      s.dcat ? out_cat.data_ptr<long>() : nullptr,
       (const unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, (int)batch_size, pool_size, q, dc, dcat,
+      (int)n_batches, s.batch_size, s.pool_size, s.q, s.dc, s.dcat,
       (int)max_cat, (float)visibility,
       (float)gravity, (float)neg_gravity, (float)norm_scale,
       (float)cat_factor, (float)p_same, (unsigned long long)seed,
@@ -944,22 +1093,22 @@ void eagle_update(torch::Tensor pool_cont, torch::Tensor pool_cat,
                   int64_t n_batches,
                   double penalize_factor, double perturbation_lower_bound,
                   double base_perturbation, int64_t seed) {
-  const int batch_size = batch_cont.size(0);
-  const int q = batch_cont.size(1);
-  const int dc = batch_cont.size(2);
-  const int dcat = batch_cat.size(2);
+  const EagleShape s = check_eagle_update_args(
+      pool_cont, pool_cat, rewards, perturbations, batch_cont, batch_cat,
+      batch_rewards, cat_sizes, best_reward, iter_counter, n_batches,
+      torch::kFloat32);
   launch_eagle_update(
       pool_cont.data_ptr<float>(),
-      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
       rewards.data_ptr<float>(), perturbations.data_ptr<float>(),
       batch_cont.data_ptr<float>(),
-      dcat ? batch_cat.data_ptr<long>() : nullptr,
+      s.dcat ? batch_cat.data_ptr<long>() : nullptr,
       batch_rewards.data_ptr<float>(),
-      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
       best_reward.data_ptr<float>(),
       (unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, batch_size, q, dc,
-      dcat, (float)penalize_factor, (float)perturbation_lower_bound,
+      (int)n_batches, s.batch_size, s.q, s.dc,
+      s.dcat, (float)penalize_factor, (float)perturbation_lower_bound,
       (float)base_perturbation, (unsigned long long)seed,
       current_stream());
 }
@@ -1023,20 +1172,6 @@ int64_t eagle_sweep(
 }
 
 // -- fp64 parity-mode bindings -------------------------------------------------
-
-torch::Tensor check_f64(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat64, name, " must be fp64");
-  return t.contiguous();
-}
-
-// Tensors the Eagle kernels update in place: never copied.
-void check_inplace(const torch::Tensor& t, torch::ScalarType dtype,
-                   const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype &&
-              t.is_contiguous(), name,
-              " must be a contiguous GPU tensor of the kernel's dtype");
-}
 
 // Runs the three fp64 scorer kernels on the current stream. `want_score`
 // selects the (B,) acquisition score; otherwise mean and sd are written.
@@ -1135,53 +1270,18 @@ std::vector<torch::Tensor> eagle_suggest_f64(
     double visibility, double gravity, double neg_gravity,
     double norm_scale, double cat_factor, double p_same, int64_t seed,
     torch::Tensor out_cont, torch::Tensor out_cat, int64_t max_cat) {
-  pool_cont = check_f64(pool_cont, "pool_cont");
-  rewards = check_f64(rewards, "rewards");
-  perturbations = check_f64(perturbations, "perturbations");
-  TORCH_CHECK(iter_counter.scalar_type() == torch::kInt64 &&
-              iter_counter.is_cuda() && iter_counter.is_contiguous() &&
-              iter_counter.numel() >= 2,
-              "iter_counter must be int64 cuda with >= 2 slots");
-  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3,
-              "pool_cont / pool_cat must be (P, q, D*)");
-  TORCH_CHECK(pool_cat.is_cuda() &&
-              pool_cat.scalar_type() == torch::kInt64 &&
-              cat_sizes.is_cuda() &&
-              cat_sizes.scalar_type() == torch::kInt64,
-              "pool_cat / cat_sizes must be int64 GPU tensors");
-  pool_cat = pool_cat.contiguous();
-  cat_sizes = cat_sizes.contiguous();
-  const int pool_size = pool_cont.size(0);
-  const int q = pool_cont.size(1);
-  const int dc = pool_cont.size(2);
-  const int dcat = pool_cat.size(2);
-  // The kernel keeps scale[MAX_POOL] in LDS and indexes the pool by
-  // batch_start + b < n_batches * batch_size.
-  TORCH_CHECK(pool_size >= 1 && pool_size <= 128,
-              "eagle_suggest_f64 supports 1 <= pool <= 128");
-  TORCH_CHECK(q >= 1 && q <= 16, "eagle_suggest_f64 supports q <= 16");
-  TORCH_CHECK(batch_size >= 1 && n_batches >= 1 &&
-              n_batches * batch_size <= pool_size,
-              "n_batches * batch_size must not exceed the pool");
-  TORCH_CHECK(pool_cat.size(0) == pool_size && pool_cat.size(1) == q &&
-              rewards.numel() == pool_size &&
-              perturbations.numel() == pool_size &&
-              cat_sizes.numel() == dcat, "pool shape mismatch");
-  check_inplace(out_cont, torch::kFloat64, "out_cont");
-  check_inplace(out_cat, torch::kInt64, "out_cat");
-  TORCH_CHECK(out_cont.numel() == batch_size * q * dc &&
-              out_cat.numel() == batch_size * q * dcat,
-              "out_cont / out_cat must be (batch, q, D*)");
-  TORCH_CHECK(dcat == 0 || max_cat >= 1, "max_cat must be >= 1");
+  const EagleShape s = check_eagle_suggest_args(
+      pool_cont, pool_cat, rewards, perturbations, cat_sizes, iter_counter,
+      n_batches, batch_size, out_cont, out_cat, max_cat, torch::kFloat64);
   launch_eagle_suggest_f64(
       pool_cont.data_ptr<double>(),
-      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
       rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
-      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
       out_cont.data_ptr<double>(),
-      dcat ? out_cat.data_ptr<long>() : nullptr,
+      s.dcat ? out_cat.data_ptr<long>() : nullptr,
       (const unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, (int)batch_size, pool_size, q, dc, dcat,
+      (int)n_batches, s.batch_size, s.pool_size, s.q, s.dc, s.dcat,
       (int)max_cat, visibility, gravity, neg_gravity, norm_scale,
       cat_factor, p_same, (unsigned long long)seed, current_stream());
   return {out_cont, out_cat};
@@ -1195,51 +1295,21 @@ void eagle_update_f64(torch::Tensor pool_cont, torch::Tensor pool_cat,
                       int64_t n_batches, double penalize_factor,
                       double perturbation_lower_bound,
                       double base_perturbation, int64_t seed) {
-  check_inplace(pool_cont, torch::kFloat64, "pool_cont");
-  check_inplace(pool_cat, torch::kInt64, "pool_cat");
-  check_inplace(rewards, torch::kFloat64, "rewards");
-  check_inplace(perturbations, torch::kFloat64, "perturbations");
-  check_inplace(best_reward, torch::kFloat64, "best_reward");
-  check_inplace(iter_counter, torch::kInt64, "iter_counter");
-  batch_cont = check_f64(batch_cont, "batch_cont");
-  batch_rewards = check_f64(batch_rewards, "batch_rewards");
-  TORCH_CHECK(batch_cat.is_cuda() &&
-              batch_cat.scalar_type() == torch::kInt64 &&
-              cat_sizes.is_cuda() &&
-              cat_sizes.scalar_type() == torch::kInt64,
-              "batch_cat / cat_sizes must be int64 GPU tensors");
-  batch_cat = batch_cat.contiguous();
-  cat_sizes = cat_sizes.contiguous();
-  TORCH_CHECK(pool_cont.dim() == 3 && pool_cat.dim() == 3 &&
-              batch_cont.dim() == 3 && batch_cat.dim() == 3,
-              "pool / batch tensors must be (rows, q, D*)");
-  const int pool_size = pool_cont.size(0);
-  const int batch_size = batch_cont.size(0);
-  const int q = batch_cont.size(1);
-  const int dc = batch_cont.size(2);
-  const int dcat = batch_cat.size(2);
-  TORCH_CHECK(batch_size >= 1 && n_batches >= 1 &&
-              n_batches * batch_size <= pool_size,
-              "n_batches * batch_size must not exceed the pool");
-  TORCH_CHECK(pool_cont.size(1) == q && pool_cont.size(2) == dc &&
-              pool_cat.size(0) == pool_size && pool_cat.size(1) == q &&
-              pool_cat.size(2) == dcat && batch_cat.size(0) == batch_size &&
-              batch_cat.size(1) == q && rewards.numel() == pool_size &&
-              perturbations.numel() == pool_size &&
-              batch_rewards.numel() == batch_size &&
-              cat_sizes.numel() == dcat && best_reward.numel() >= 1 &&
-              iter_counter.numel() >= 2, "pool / batch shape mismatch");
+  const EagleShape s = check_eagle_update_args(
+      pool_cont, pool_cat, rewards, perturbations, batch_cont, batch_cat,
+      batch_rewards, cat_sizes, best_reward, iter_counter, n_batches,
+      torch::kFloat64);
   launch_eagle_update_f64(
       pool_cont.data_ptr<double>(),
-      dcat ? pool_cat.data_ptr<long>() : nullptr,
+      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
       rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
       batch_cont.data_ptr<double>(),
-      dcat ? batch_cat.data_ptr<long>() : nullptr,
+      s.dcat ? batch_cat.data_ptr<long>() : nullptr,
       batch_rewards.data_ptr<double>(),
-      dcat ? cat_sizes.data_ptr<long>() : nullptr,
+      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
       best_reward.data_ptr<double>(),
       (unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, batch_size, q, dc, dcat, penalize_factor,
+      (int)n_batches, s.batch_size, s.q, s.dc, s.dcat, penalize_factor,
       perturbation_lower_bound, base_perturbation,
       (unsigned long long)seed, current_stream());
 }
@@ -1273,7 +1343,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("posterior_scores", &posterior_scores,
         "Fused GP posterior + acquisition + trust region (gfx950)");
   m.def("batched_potrf", &batched_potrf,
-        "Batched lower Cholesky, one workgroup per matrix (gfx950)");
+        "Batched Cholesky K (R, N, N) fp32 -> (L, info). Only the lower "
+        "triangle of L is defined; the strict upper triangle holds "
+        "unspecified values. info[r] is the 1-based first column whose "
+        "pivot is not > 0 (zero, negative or NaN), 0 on success (gfx950)");
   m.def("batched_trsv_lower", &batched_trsv_lower,
         "Batched forward substitution L z = b (gfx950)");
   m.def("gram_matern52_fp8_pre", &gram_matern52_fp8_pre,

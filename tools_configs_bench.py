@@ -9,6 +9,11 @@
 
 Each reports suggest() wall-clock (mean over a few calls, first call
 excluded: it pays hipGraph/megakernel warmup).
+
+Usage: tools_configs_bench.py [2|3|4|5] [--qei-scorer {torch,hip}]
+--qei-scorer selects config 3's qEI set scorer (default torch, so recorded
+numbers stay comparable); config 3 also prints every repetition, the
+sweep-only time (fit cached) and whether the sweep ran as a hipGraph.
 """
 
 import json
@@ -53,10 +58,10 @@ def preload(designer, dim, n_trials, metrics=('obj',), seed=0):
   designer.update(CompletedTrials(trials), ActiveTrials())
 
 
-def timed_suggest(designer, count=1, reps=3):
+def timed_suggest(designer, count=1, reps=3, times=None):
   designer.suggest(count)  # warmup (fit + graph capture)
   torch.cuda.synchronize()
-  times = []
+  times = [] if times is None else times
   uid = 10_000_000
   for _ in range(reps):
     t0 = time.perf_counter()
@@ -76,7 +81,7 @@ def run_one(which: str) -> None:
   main(only=which)
 
 
-def main(only=None):
+def main(only=None, qei_scorer='torch'):
   out = {}
 
   # Config 2: 8D, N=500, bf16 grams.
@@ -92,7 +97,7 @@ def main(only=None):
 
   # Config 3: 20D, N=2000, qEI count=8.
   if only in (None, '3'):
-    _config3(out)
+    _config3(out, qei_scorer)
 
   # Config 4: 50D, N=10000, 1.25M evals (per-GPU slice of 10M DP=8).
   if only in (None, '4'):
@@ -111,13 +116,35 @@ def main(only=None):
     json.dump(old, f, indent=2)
 
 
-def _config3(out):
+def _config3(out, qei_scorer='torch'):
   d = VizierGPBandit(make_problem(20), GPBanditConfig(
-      max_evaluations=75000, acquisition='qei', device='cuda'), seed=0)
+      max_evaluations=75000, acquisition='qei', qei_scorer=qei_scorer,
+      device='cuda'), seed=0)
   preload(d, 20, 2000)
-  ms = timed_suggest(d, count=8)
-  out['config3_20d_n2000_qei8'] = ms
-  print(f'config 3 (20D N=2000 qEI q=8): {ms:.1f} ms/suggest(8)',
+  times = []
+  ms = timed_suggest(d, count=8, reps=5, times=times)
+  # The default scorer keeps the historical key.
+  key = 'config3_20d_n2000_qei8' + ('' if qei_scorer == 'torch'
+                                    else f'_{qei_scorer}')
+  out[key] = ms
+  print(f'config 3 (20D N=2000 qEI q=8, {qei_scorer} scorer): {ms:.1f} '
+        'ms/suggest(8); reps ' + ' '.join(f'{t * 1e3:.1f}' for t in times),
+        flush=True)
+  # Sweep alone: the fit is cached after the first call.
+  d._fit()
+  sweeps = []
+  for _ in range(5):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d._gp_suggestions(8)
+    torch.cuda.synchronize()
+    sweeps.append((time.perf_counter() - t0) * 1e3)
+  opt = d._last_optimizer
+  out[key + '_sweep_ms'] = float(np.median(sweeps))
+  out[key + '_used_graph'] = bool(opt.last_used_graph)
+  print(f'config 3 sweep only: median {np.median(sweeps):.1f} ms, min '
+        f'{min(sweeps):.1f}, max {max(sweeps):.1f}; hipGraph path: '
+        f'{opt.last_used_graph} (graph error: {opt.last_graph_error})',
         flush=True)
 
 
@@ -147,5 +174,11 @@ def _config5(out):
 
 
 if __name__ == '__main__':
-  import sys as _sys
-  main(only=_sys.argv[1] if len(_sys.argv) > 1 else None)
+  import argparse
+  parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+  parser.add_argument('only', nargs='?', choices=['2', '3', '4', '5'],
+                      help='run this config alone (default: all)')
+  parser.add_argument('--qei-scorer', choices=['torch', 'hip'],
+                      default='torch', help="config 3's qEI set scorer")
+  args = parser.parse_args()
+  main(only=args.only, qei_scorer=args.qei_scorer)

@@ -37,6 +37,7 @@ from vizier_amd._src.algorithms.designers.quasi_random import (
 from vizier_amd._src.algorithms.optimizers.eagle import (
     CandidateBatch,
     EagleStrategyConfig,
+    HIP_MAX_PARALLEL,
 )
 from vizier_amd._src.algorithms.optimizers.vectorized import (
     EagleFeatureCodec,
@@ -75,6 +76,17 @@ class GPBanditConfig:
   use_trust_region: bool = True
   num_scalarizations: int = 1000  # multi-objective
   scorer_gram_dtype: str = 'fp32'  # 'fp32'|'bf16'|'fp8' candidate grams
+  # acquisition='qei' set scorer: 'torch' (default: batched einsums +
+  # library Cholesky, eager sweep) or 'hip' (opt-in: the fused
+  # qei_score.hip kernels, GPU + float32 only). With a plain GP posterior
+  # that has K_inv, 'hip' scores a set in one capturable op and the sweep
+  # runs through the hipGraph path; with a linear-kernel posterior or no
+  # K_inv only the Cholesky + Monte-Carlo stage moves to HIP and the
+  # sweep stays eager. More than 16 suggestions per call exceed the
+  # kernels' set size and run the torch scorer, as oversized Eagle pools
+  # run the torch step. The captured sweep selects from the final pool
+  # and sums in another order, so suggestions can differ from 'torch'.
+  qei_scorer: str = 'torch'
   ensemble_size: int = 1   # best-N ARD restarts mixed (gp_models.py:201)
   # Additive continuous-only linear kernel scale (gp_bandit.py:131
   # _linear_coef; tuned_gp_models.py:204): None disables it. Posteriors
@@ -105,6 +117,9 @@ class VizierGPBandit(Designer, Predictor):
                config: Optional[GPBanditConfig] = None, *, seed: int = 0):
     self._problem = problem
     self._config = config or GPBanditConfig()
+    if self._config.qei_scorer not in ('torch', 'hip'):
+      raise ValueError("qei_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.qei_scorer!r}')
     self._seed = seed
     self._trials: List[vz.Trial] = []
     self._converter = TrialToArrayConverter(problem)
@@ -119,6 +134,7 @@ class VizierGPBandit(Designer, Predictor):
     self._last_fit_count = -1
     self._x_cache = None
     self._y_cache = None
+    self._last_optimizer = None  # the most recent sweep's optimizer
 
   @classmethod
   def from_problem(cls, problem: vz.ProblemStatement,
@@ -504,6 +520,17 @@ class VizierGPBandit(Designer, Predictor):
       eps_dev = torch.randn(128, 1, count, generator=g).to(
           self._device, cfg.dtype)
 
+      if cfg.qei_scorer == 'hip':
+        if not self._x.is_cuda or cfg.dtype != torch.float32:
+          raise ValueError(
+              "qei_scorer='hip' needs a GPU device and dtype float32, got "
+              f'device {self._x.device} and {cfg.dtype}')
+        # Sets larger than the kernels' q <= 16 run the torch scorer below
+        # (as oversized Eagle pools run the torch step).
+        if count <= HIP_MAX_PARALLEL:
+          return self._qei_hip_score_fn(posterior, eps_dev[:, 0, :],
+                                        best_value, trust_region), count
+
       def score_fn(batch: CandidateBatch) -> torch.Tensor:
         dense = self._codec.decode(batch)          # (B, q, D)
         mean, cov = posterior_batched_cov(posterior, dense)
@@ -554,6 +581,43 @@ class VizierGPBandit(Designer, Predictor):
     score_fn.codec_identity = self._codec.identity
     return score_fn, 1
 
+  def _qei_hip_score_fn(self, posterior, eps: torch.Tensor,
+                        best_value: float, trust_region):
+    """qEI set scorer on the qei_score.hip kernels (qei_scorer='hip').
+
+    Plain GPPosterior with K_inv: the whole scorer is ONE fused op
+    (acq_lib.QEISetScoringFunction) without host syncs, so the sweep may
+    capture it. Otherwise (linear kernel, no K_inv) the joint covariance
+    stays in torch and only its Cholesky + Monte-Carlo stage runs in HIP;
+    that composition syncs the host and is not offered for capture.
+    """
+    anchored = trust_region is None or (
+        trust_region._trusted.shape == posterior.x.shape and
+        trust_region._trusted.data_ptr() == posterior.x.data_ptr())
+    if (type(posterior) is gp_model.GPPosterior and
+        posterior.K_inv is not None and anchored):
+      scoring = acq_lib.QEISetScoringFunction(posterior, eps, best_value,
+                                              trust_region)
+
+      def score_fn(batch: CandidateBatch) -> torch.Tensor:
+        return scoring(self._codec.decode(batch))       # (B, q, D)
+      score_fn.graph_safe = True
+      return score_fn
+
+    from vizier_amd._src.ops import dispatch as ops
+    ext = ops.require_ext()
+    eps = eps.contiguous()
+
+    def score_fn(batch: CandidateBatch) -> torch.Tensor:
+      dense = self._codec.decode(batch)
+      mean, cov = posterior_batched_cov(posterior, dense)
+      scores = ext.qei_scores_from_cov(mean, cov, eps, best_value)
+      if trust_region is not None:
+        scores = trust_region.apply(dense[:, 0, :], scores)
+      return scores
+    score_fn.graph_safe = False
+    return score_fn
+
   def _gp_suggestions(self, count: int) -> List[vz.TrialSuggestion]:
     cfg = self._config
     self._fit()
@@ -570,6 +634,9 @@ class VizierGPBandit(Designer, Predictor):
         n_parallel=n_parallel,
         seed=self._seed + len(self._trials) + 7919 * shard_rank,
         device=self._device, dtype=cfg.dtype)
+    # Kept for diagnostics: last_used_graph / last_used_megakernel /
+    # last_graph_error of the most recent sweep (tools_configs_bench.py).
+    self._last_optimizer = optimizer
 
     rewards_np = self._warped_labels[:, 0].cpu().numpy() \
         if len(self._posteriors) == 1 else \

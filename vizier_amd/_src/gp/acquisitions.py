@@ -439,6 +439,53 @@ def qei_mc_scores(mean: torch.Tensor, cov: torch.Tensor,
   return (samples - best_value).clamp_min(0).amax(-1).mean(0)
 
 
+class QEISetScoringFunction:
+  """Monte-Carlo qEI over candidate sets as one fused HIP op (GPU, fp32).
+
+  dense (B, q <= 16, D) -> (B,): `posterior_batched_cov` + `qei_mc_scores`
+  + `TrustRegion.apply(dense[:, 0, :], .)` computed by qei_score.hip
+  (k-vectors, one K^-1 SGEMM, joint covariance, q x q Cholesky with the
+  diagonal fallback, max-improvement over the common draws `eps` (S, q)).
+  No host sync per call, so the sweep can capture it in a hipGraph.
+  Needs a plain GPPosterior with K_inv and a trust region anchored at the
+  posterior's training points.
+  """
+
+  def __init__(self, posterior: GPPosterior, eps: torch.Tensor,
+               best_value: float,
+               trust_region: Optional[TrustRegion] = None):
+    if posterior.K_inv is None:
+      raise ValueError('QEISetScoringFunction needs a posterior with K_inv')
+    if trust_region is not None and not (
+        trust_region._trusted.shape == posterior.x.shape and
+        trust_region._trusted.data_ptr() == posterior.x.data_ptr()):
+      raise ValueError('QEISetScoringFunction needs a trust region '
+                       'anchored at the posterior training points')
+    self.posterior = posterior
+    self.trust_region = trust_region
+    self.eps = eps.contiguous()
+    # Pre-extract scalars once so the hot loop never syncs the device.
+    self._amp = float(posterior.params.amplitude)
+    self._mean_c = float(posterior.params.mean)
+    self._best = float(best_value)
+    d = posterior.x.shape[-1]
+    if trust_region is not None:
+      self._onehot_u8 = trust_region._onehot.to(torch.uint8)
+      self._tr_radius = float(trust_region.trust_radius)
+    else:
+      self._onehot_u8 = torch.zeros(d, dtype=torch.uint8,
+                                    device=posterior.x.device)
+      self._tr_radius = 0.0
+
+  def __call__(self, dense: torch.Tensor) -> torch.Tensor:
+    from vizier_amd._src.ops import dispatch as ops
+    post = self.posterior
+    return ops.require_ext().qei_set_scores(
+        dense, post.x, post.params.lengthscales, self._amp, self._mean_c,
+        post.alpha, post.K_inv, self._onehot_u8, self.eps, self._best,
+        self._tr_radius)
+
+
 class ScoringFunction:
   """Posterior + acquisition + optional trust region, over a batch.
 

@@ -116,6 +116,15 @@ extern "C" void launch_ps_quadform_finalize(
     float amp2, float mean_c, int acq, float coef, float best_value,
     float tr_radius, hipStream_t stream);
 
+extern "C" void launch_qei_cov(
+    const float* t_ws, const float* k_ws, const float* mu_ws,
+    const float* xs, const float* inv_ls, float* mean_out, float* cov_out,
+    int b, int q, int n, int d, float amp2, float mean_c,
+    hipStream_t stream);
+extern "C" void launch_qei_mc(
+    const float* mean, const float* cov, const float* eps,
+    const float* dist, float* out, int b, int q, int s, float best_value,
+    float tr_radius, hipStream_t stream);
 extern "C" int batched_potrf_needs_scratch(int n);
 extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
                                      int r, int n, hipStream_t stream);
@@ -587,6 +596,129 @@ torch::Tensor posterior_scores_chunked(
       (float)coef, (float)best_value, (float)tr_radius,
       current_stream());
   return out;
+}
+
+// -- Monte-Carlo qEI over candidate sets (qei_score.hip) ------------------
+
+namespace {
+
+constexpr int kQeiMaxParallel = 16;  // == eagle.HIP_MAX_PARALLEL
+
+struct QeiJoint {
+  torch::Tensor mean;     // (B, q)
+  torch::Tensor cov;      // (B, q, q)
+  torch::Tensor dist_ws;  // (B*q,) min L-inf distance of EVERY member
+};
+
+// Stages A-C: k-vectors of the B*q flattened candidates, T = k @ Kinv as
+// one SGEMM (Kinv read once, as quadform_large_n does), then the joint
+// mean / covariance kernel. No N-dependent branch: B*q workgroups already
+// fill the chip, so the row-split k-vector kernel is never needed here.
+// No host sync anywhere, so the sequence is stream-capturable.
+QeiJoint qei_joint_impl(torch::Tensor xs, torch::Tensor x,
+                        torch::Tensor lengthscales, double amplitude,
+                        double mean_c, torch::Tensor alpha,
+                        torch::Tensor kinv, torch::Tensor onehot) {
+  xs = check_f32(xs, "xs");
+  TORCH_CHECK(xs.dim() == 3, "xs must be (B, q, D), got ", xs.dim(),
+              " dimensions");
+  const int64_t b = xs.size(0), q = xs.size(1), d = xs.size(2);
+  TORCH_CHECK(b >= 1, "xs must hold at least one candidate set");
+  TORCH_CHECK(q >= 1 && q <= kQeiMaxParallel, "qEI set scorer supports ",
+              "1 <= q <= ", kQeiMaxParallel, ", got q = ", q);
+  TORCH_CHECK(d <= 512, "qEI set scorer supports D <= 512, got ", d);
+  x = check_f32(x, "x");
+  lengthscales = check_f32(lengthscales, "lengthscales");
+  alpha = check_f32(alpha, "alpha");
+  kinv = check_f32(kinv, "kinv");
+  auto flat = xs.view({b * q, d});
+  check_scorer_args(flat, x, lengthscales, alpha, kinv, onehot);
+  onehot = onehot.contiguous();
+  const int64_t n = x.size(0);
+  TORCH_CHECK(b * q * std::max<int64_t>(n, q) < (int64_t{1} << 31),
+              "qEI set scorer workspace too large");
+  const float amp2 = (float)(amplitude * amplitude);
+  auto inv_ls = 1.0f / lengthscales;
+  auto k_ws = torch::empty({b * q, n}, xs.options());
+  auto mu_ws = torch::empty({b * q}, xs.options());
+  auto dist_ws = torch::empty({b * q}, xs.options());
+  launch_ps_kvec(flat.data_ptr<float>(), x.data_ptr<float>(),
+                 inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
+                 onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
+                 mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
+                 (int)(b * q), (int)n, (int)d, amp2, current_stream());
+  auto t_ws = at::matmul(k_ws, kinv).contiguous();
+  auto mean = torch::empty({b, q}, xs.options());
+  auto cov = torch::empty({b, q, q}, xs.options());
+  launch_qei_cov(t_ws.data_ptr<float>(), k_ws.data_ptr<float>(),
+                 mu_ws.data_ptr<float>(), xs.data_ptr<float>(),
+                 inv_ls.data_ptr<float>(), mean.data_ptr<float>(),
+                 cov.data_ptr<float>(), (int)b, (int)q, (int)n, (int)d,
+                 amp2, (float)mean_c, current_stream());
+  return {mean, cov, dist_ws};
+}
+
+// Stage D. dist_ws: (B*q,) distances (member 0 of each set is read), or
+// undefined for no trust region.
+torch::Tensor qei_mc_impl(const torch::Tensor& mean,
+                          const torch::Tensor& cov, torch::Tensor eps,
+                          double best_value, const torch::Tensor& dist_ws,
+                          double tr_radius) {
+  const int64_t b = mean.size(0), q = mean.size(1);
+  eps = check_f32(eps, "eps");
+  TORCH_CHECK(eps.dim() == 2, "eps must be (S, q)");
+  TORCH_CHECK(eps.size(1) == q, "eps must have q = ", q,
+              " columns, got ", eps.size(1));
+  const int64_t s = eps.size(0);
+  TORCH_CHECK(s >= 1, "eps must hold at least one sample");
+  TORCH_CHECK(s * q < (int64_t{1} << 31), "eps too large");
+  auto out = torch::empty({b}, mean.options());
+  launch_qei_mc(mean.data_ptr<float>(), cov.data_ptr<float>(),
+                eps.data_ptr<float>(),
+                dist_ws.defined() ? dist_ws.data_ptr<float>() : nullptr,
+                out.data_ptr<float>(), (int)b, (int)q, (int)s,
+                (float)best_value, (float)tr_radius, current_stream());
+  return out;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> qei_joint_mean_cov(
+    torch::Tensor xs, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot) {
+  auto j = qei_joint_impl(xs, x, lengthscales, amplitude, mean_c, alpha,
+                          kinv, onehot);
+  const int64_t b = j.mean.size(0), q = j.mean.size(1);
+  return {j.mean, j.cov, j.dist_ws.view({b, q}).select(1, 0).contiguous()};
+}
+
+torch::Tensor qei_scores_from_cov(torch::Tensor mean, torch::Tensor cov,
+                                  torch::Tensor eps, double best_value) {
+  mean = check_f32(mean, "mean");
+  cov = check_f32(cov, "cov");
+  TORCH_CHECK(mean.dim() == 2, "mean must be (B, q)");
+  const int64_t b = mean.size(0), q = mean.size(1);
+  TORCH_CHECK(b >= 1, "mean must hold at least one candidate set");
+  TORCH_CHECK(q >= 1 && q <= kQeiMaxParallel, "qEI set scorer supports ",
+              "1 <= q <= ", kQeiMaxParallel, ", got q = ", q);
+  TORCH_CHECK(cov.dim() == 3 && cov.size(0) == b && cov.size(1) == q &&
+              cov.size(2) == q, "cov must be (", b, ", ", q, ", ", q, ")");
+  return qei_mc_impl(mean, cov, eps, best_value, torch::Tensor(), 0.0);
+}
+
+torch::Tensor qei_set_scores(
+    torch::Tensor xs, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot, torch::Tensor eps,
+    double best_value, double tr_radius) {
+  // Check eps before anything is launched.
+  TORCH_CHECK(xs.dim() == 3 && eps.dim() == 2 &&
+              eps.size(1) == xs.size(1),
+              "eps must be (S, q) with q = xs.size(1)");
+  auto j = qei_joint_impl(xs, x, lengthscales, amplitude, mean_c, alpha,
+                          kinv, onehot);
+  return qei_mc_impl(j.mean, j.cov, eps, best_value, j.dist_ws, tr_radius);
 }
 
 torch::Tensor posterior_scores_bf16(
@@ -1361,6 +1493,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Chunked scorer with cached-bf16 candidate grams (gfx950)");
   m.def("posterior_scores_chunked", &posterior_scores_chunked,
         "3-kernel chunked GP posterior scorer (chip-filling, gfx950)");
+  m.def("qei_joint_mean_cov", &qei_joint_mean_cov,
+        "Joint posterior (mean, cov, member-0 dist) of candidate sets "
+        "xs (B, q <= 16, D); assumes a symmetric kinv (gfx950)");
+  m.def("qei_scores_from_cov", &qei_scores_from_cov,
+        "Monte-Carlo qEI of (mean, cov) sets: q x q Cholesky with the "
+        "diagonal fallback + max-improvement, no trust region (gfx950)");
+  m.def("qei_set_scores", &qei_set_scores,
+        "Fused Monte-Carlo qEI set scorer + trust region by member 0, "
+        "stream-capturable (gfx950)");
   m.def("eagle_suggest", &eagle_suggest,
         "Fused Eagle suggest step (gfx950)");
   m.def("eagle_update", &eagle_update, "Fused Eagle update step (gfx950)");

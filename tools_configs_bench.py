@@ -7,13 +7,18 @@
      scaling itself)
   5: Multi-objective HV-scalarized UCB + trust region, 30D, fp8 grams
 
+  setpe: GP-UCB-PE set-PE batch, 20D, N=1000, suggest count=8 with
+     optimize_set_acquisition_for_exploration (only when asked for by name)
+
 Each reports suggest() wall-clock (mean over a few calls, first call
 excluded: it pays hipGraph/megakernel warmup).
 
-Usage: tools_configs_bench.py [2|3|4|5] [--qei-scorer {torch,hip}]
---qei-scorer selects config 3's qEI set scorer (default torch, so recorded
-numbers stay comparable); config 3 also prints every repetition, the
-sweep-only time (fit cached) and whether the sweep ran as a hipGraph.
+Usage: tools_configs_bench.py [2|3|4|5|setpe] [--qei-scorer {torch,hip}]
+                              [--set-pe-scorer {torch,hip}]
+--qei-scorer selects config 3's qEI set scorer and --set-pe-scorer the
+set-PE scorer of config setpe (default torch, so recorded numbers stay
+comparable); these two configs also print every repetition, the sweep-only
+time (fit cached) and whether the sweep ran as a hipGraph.
 """
 
 import json
@@ -81,7 +86,7 @@ def run_one(which: str) -> None:
   main(only=which)
 
 
-def main(only=None, qei_scorer='torch'):
+def main(only=None, qei_scorer='torch', set_pe_scorer='torch'):
   out = {}
 
   # Config 2: 8D, N=500, bf16 grams.
@@ -106,6 +111,9 @@ def main(only=None, qei_scorer='torch'):
   # Config 5: 30D MO + trust region, fp8 grams.
   if only in (None, '5'):
     _config5(out)
+
+  if only == 'setpe':
+    _config_setpe(out, set_pe_scorer)
 
   print(json.dumps(out))
   import os
@@ -148,6 +156,41 @@ def _config3(out, qei_scorer='torch'):
         flush=True)
 
 
+def _config_setpe(out, set_pe_scorer='torch'):
+  from vizier_amd._src.algorithms.designers.gp_ucb_pe import (
+      UCBPEConfig,
+      VizierGPUCBPEBandit,
+  )
+  d = VizierGPUCBPEBandit(make_problem(20), UCBPEConfig(
+      max_evaluations=75000, optimize_set_acquisition_for_exploration=True,
+      set_pe_scorer=set_pe_scorer, device='cuda'), seed=0)
+  preload(d, 20, 1000)
+  times = []
+  ms = timed_suggest(d, count=8, reps=3, times=times)
+  key = f'setpe_20d_n1000_q8_{set_pe_scorer}'
+  out[key] = ms
+  print(f'config setpe (20D N=1000 suggest(8), {set_pe_scorer} scorer): '
+        f'{ms:.1f} ms/suggest(8); reps '
+        + ' '.join(f'{t * 1e3:.1f}' for t in times), flush=True)
+  # The set phase alone (variance posterior + the 7-member set sweep): the
+  # fit is cached after the first call.
+  d._fit()
+  sweeps = []
+  for _ in range(5):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d._optimize_set(d._posterior.x, 7)
+    torch.cuda.synchronize()
+    sweeps.append((time.perf_counter() - t0) * 1e3)
+  opt = d._last_set_optimizer
+  out[key + '_sweep_ms'] = float(np.median(sweeps))
+  out[key + '_used_graph'] = bool(opt.last_used_graph)
+  print(f'config setpe set sweep only: median {np.median(sweeps):.1f} ms, '
+        f'min {min(sweeps):.1f}, max {max(sweeps):.1f}; hipGraph path: '
+        f'{opt.last_used_graph} (graph error: {opt.last_graph_error})',
+        flush=True)
+
+
 def _config4(out):
   d = VizierGPBandit(make_problem(50), GPBanditConfig(
       max_evaluations=1_250_000, device='cuda'), seed=0)
@@ -176,9 +219,13 @@ def _config5(out):
 if __name__ == '__main__':
   import argparse
   parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-  parser.add_argument('only', nargs='?', choices=['2', '3', '4', '5'],
-                      help='run this config alone (default: all)')
+  parser.add_argument('only', nargs='?',
+                      choices=['2', '3', '4', '5', 'setpe'],
+                      help='run this config alone (default: 2-5)')
   parser.add_argument('--qei-scorer', choices=['torch', 'hip'],
                       default='torch', help="config 3's qEI set scorer")
+  parser.add_argument('--set-pe-scorer', choices=['torch', 'hip'],
+                      default='torch', help="config setpe's set-PE scorer")
   args = parser.parse_args()
-  main(only=args.only, qei_scorer=args.qei_scorer)
+  main(only=args.only, qei_scorer=args.qei_scorer,
+       set_pe_scorer=args.set_pe_scorer)

@@ -32,6 +32,7 @@ from vizier_amd._src.algorithms.designers import gp_bandit
 from vizier_amd._src.algorithms.optimizers.eagle import (
     CandidateBatch,
     EagleStrategyConfig,
+    HIP_MAX_PARALLEL,
 )
 from vizier_amd._src.algorithms.optimizers.vectorized import (
     EagleFeatureCodec,
@@ -67,6 +68,17 @@ class UCBPEConfig:
   # completed + pending trials) — intra-batch correlation is penalized,
   # so the batch decorrelates, unlike the sequential summed-stddev fill.
   optimize_set_acquisition_for_exploration: bool = False
+  # Set-PE scorer: 'torch' (default: predict + batched covariance +
+  # library Cholesky, eager sweep) or 'hip' (opt-in: the fused
+  # setpe_score.hip scorer, GPU + float32 only). With plain GP posteriors
+  # that have K_inv and at most 16 set members, 'hip' scores a set in one
+  # capturable op and the sweep runs through the hipGraph path; a
+  # linear-kernel posterior, a posterior without K_inv or a larger set
+  # runs the torch scorer. The captured sweep selects from the final pool
+  # and the fp32 sums run in another order, so a near-singular set can
+  # land on the other side of "pivot > 0" and suggestions can differ from
+  # 'torch'.
+  set_pe_scorer: str = 'torch'
   max_evaluations: int = 75000
   suggestion_batch_size: int = 25
   num_seed_trials: int = 2
@@ -86,6 +98,9 @@ class VizierGPUCBPEBandit(Designer):
                config: Optional[UCBPEConfig] = None, *, seed: int = 0):
     self._problem = problem
     self._config = config or UCBPEConfig()
+    if self._config.set_pe_scorer not in ('torch', 'hip'):
+      raise ValueError("set_pe_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.set_pe_scorer!r}')
     self._seed = seed
     self._rng = np.random.default_rng(seed)
     self._completed: List[vz.Trial] = []
@@ -99,6 +114,7 @@ class VizierGPUCBPEBandit(Designer):
     self._mt_raw = None           # joint multitask warm start
     self._last_fit_count = -1
     self._last_suggest_completed = 0
+    self._last_set_optimizer = None  # the most recent set-PE sweep's
     from vizier_amd._src.algorithms.designers.quasi_random import (
         QuasiRandomDesigner,
     )
@@ -342,6 +358,31 @@ class VizierGPUCBPEBandit(Designer):
     (q, D) feature rows.
     """
     cfg = self._config
+    score_fn = self._set_pe_score_fn(x_all, q)
+    factory = VectorizedOptimizerFactory(
+        eagle_config=EagleStrategyConfig(),
+        max_evaluations=cfg.max_evaluations,
+        suggestion_batch_size=cfg.suggestion_batch_size)
+    optimizer = factory(
+        n_continuous=self._codec.n_continuous,
+        categorical_sizes=self._codec.categorical_sizes, n_parallel=q,
+        seed=self._seed + len(self._completed) + x_all.shape[0],
+        device=self._device, dtype=cfg.dtype)
+    # Kept for diagnostics: last_used_graph / last_graph_error of the most
+    # recent set-PE sweep (tools_configs_bench.py).
+    self._last_set_optimizer = optimizer
+    results = optimizer.optimize(score_fn, count=1)
+    return self._codec.decode(results.features)[0]   # (q, D)
+
+  def _set_pe_score_fn(self, x_all: torch.Tensor, q: int):
+    """The set-PE scorer of `_optimize_set`: CandidateBatch -> (B,).
+
+    set_pe_scorer='hip' with q <= 16 and plain GP posteriors that have
+    K_inv: ONE fused op (acq_lib.SetPEScoringFunction) without host syncs,
+    offered for capture. Otherwise the torch closure, which syncs the host
+    (library Cholesky) and is not.
+    """
+    cfg = self._config
     posterior = self._posterior
     if isinstance(posterior, gp_model.EnsembleGPPosterior):
       posterior = posterior.members[0]
@@ -353,6 +394,25 @@ class VizierGPUCBPEBandit(Designer):
       ucb_obs = mean_obs + cfg.ucb_coefficient * stddev_obs
       threshold = mean_obs[int(torch.argmax(ucb_obs))]
     var_post = self._variance_posterior(x_all, posterior)
+
+    if cfg.set_pe_scorer == 'hip':
+      if not x_all.is_cuda or cfg.dtype != torch.float32:
+        raise ValueError(
+            "set_pe_scorer='hip' needs a GPU device and dtype float32, got "
+            f'device {x_all.device} and {cfg.dtype}')
+      # Sets larger than the kernels' q <= 16 and posteriors outside the
+      # fused-scorer contract run the torch scorer below.
+      if (q <= HIP_MAX_PARALLEL and self._fusable(posterior) and
+          self._fusable(var_post, x_all)):
+        scoring = acq_lib.SetPEScoringFunction(
+            posterior, var_post, float(threshold),
+            cfg.explore_region_ucb_coefficient,
+            cfg.cb_violation_penalty_coefficient, trust_region)
+
+        def hip_score_fn(batch: CandidateBatch) -> torch.Tensor:
+          return scoring(self._codec.decode(batch))    # (B, q, D)
+        hip_score_fn.graph_safe = True
+        return hip_score_fn
 
     def score_fn(batch: CandidateBatch) -> torch.Tensor:
       xs = self._codec.decode(batch)                 # (B, q, D)
@@ -384,18 +444,7 @@ class VizierGPUCBPEBandit(Designer):
               dist > r, -1e4 - dist, torch.zeros_like(dist)).sum(-1)
       return scores
     score_fn.graph_safe = False  # rocSOLVER cholesky: no capture
-
-    factory = VectorizedOptimizerFactory(
-        eagle_config=EagleStrategyConfig(),
-        max_evaluations=cfg.max_evaluations,
-        suggestion_batch_size=cfg.suggestion_batch_size)
-    optimizer = factory(
-        n_continuous=self._codec.n_continuous,
-        categorical_sizes=self._codec.categorical_sizes, n_parallel=q,
-        seed=self._seed + len(self._completed) + x_all.shape[0],
-        device=self._device, dtype=cfg.dtype)
-    results = optimizer.optimize(score_fn, count=1)
-    return self._codec.decode(results.features)[0]   # (q, D)
+    return score_fn
 
   @staticmethod
   def _fusable(post, x_all: Optional[torch.Tensor] = None) -> bool:

@@ -125,6 +125,11 @@ extern "C" void launch_qei_mc(
     const float* mean, const float* cov, const float* eps,
     const float* dist, float* out, int b, int q, int s, float best_value,
     float tr_radius, hipStream_t stream);
+extern "C" void launch_setpe_logdet(
+    const float* cov, const float* mean, const float* sd, const float* dist,
+    float* out, int b, int q, float jitter, float threshold,
+    float explore_coef, float penalty_coef, float tr_radius,
+    hipStream_t stream);
 extern "C" int batched_potrf_needs_scratch(int n);
 extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
                                      int r, int n, hipStream_t stream);
@@ -926,6 +931,107 @@ std::vector<torch::Tensor> posterior_mean_std_fp8(
   return {mean, sd, dist_ws};
 }
 
+// -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
+
+namespace {
+
+// The tail: one wave per set. mean / sd / dist hold one value per member
+// of the flattened batch; dist undefined means no trust region.
+torch::Tensor setpe_tail_impl(const torch::Tensor& cov,
+                              const torch::Tensor& mean,
+                              const torch::Tensor& sd,
+                              const torch::Tensor& dist, double jitter,
+                              double threshold, double explore_coef,
+                              double penalty_coef, double tr_radius) {
+  const int64_t b = cov.size(0), q = cov.size(1);
+  auto out = torch::empty({b}, cov.options());
+  launch_setpe_logdet(cov.data_ptr<float>(), mean.data_ptr<float>(),
+                      sd.data_ptr<float>(),
+                      dist.defined() ? dist.data_ptr<float>() : nullptr,
+                      out.data_ptr<float>(), (int)b, (int)q, (float)jitter,
+                      (float)threshold, (float)explore_coef,
+                      (float)penalty_coef, (float)tr_radius,
+                      current_stream());
+  return out;
+}
+
+}  // namespace
+
+torch::Tensor setpe_scores_from_cov(
+    torch::Tensor cov, torch::Tensor mean, torch::Tensor sd,
+    c10::optional<torch::Tensor> dist, double jitter, double threshold,
+    double explore_coef, double penalty_coef, double tr_radius) {
+  cov = check_f32(cov, "cov");
+  mean = check_f32(mean, "mean");
+  sd = check_f32(sd, "sd");
+  TORCH_CHECK(cov.dim() == 3 && cov.size(1) == cov.size(2),
+              "cov must be (B, q, q)");
+  const int64_t b = cov.size(0), q = cov.size(1);
+  TORCH_CHECK(b >= 1, "cov must hold at least one candidate set");
+  TORCH_CHECK(q >= 1 && q <= kQeiMaxParallel, "set-PE scorer supports ",
+              "1 <= q <= ", kQeiMaxParallel, ", got q = ", q);
+  TORCH_CHECK(b * q * q < (int64_t{1} << 31), "cov too large");
+  TORCH_CHECK(mean.numel() == b * q, "mean must have B q = ", b * q,
+              " elements, got ", mean.numel());
+  TORCH_CHECK(sd.numel() == b * q, "sd must have B q = ", b * q,
+              " elements, got ", sd.numel());
+  torch::Tensor dist_t;
+  if (dist.has_value()) {
+    dist_t = check_f32(*dist, "dist");
+    TORCH_CHECK(dist_t.numel() == b * q, "dist must have B q = ", b * q,
+                " elements, got ", dist_t.numel());
+  }
+  return setpe_tail_impl(cov, mean, sd, dist_t, jitter, threshold,
+                         explore_coef, penalty_coef, tr_radius);
+}
+
+torch::Tensor setpe_set_scores(
+    torch::Tensor xs, torch::Tensor post_x, torch::Tensor post_alpha,
+    torch::Tensor post_kinv, double post_mean_c, torch::Tensor all_x,
+    torch::Tensor all_kinv, torch::Tensor lengthscales, double amplitude,
+    torch::Tensor onehot, double threshold, double explore_coef,
+    double penalty_coef, double tr_radius) {
+  // Every operand of BOTH posteriors is checked here, before the first
+  // launch; the stages below repeat their own checks on the same values.
+  xs = check_f32(xs, "xs");
+  TORCH_CHECK(xs.dim() == 3, "xs must be (B, q, D), got ", xs.dim(),
+              " dimensions");
+  const int64_t b = xs.size(0), q = xs.size(1), d = xs.size(2);
+  TORCH_CHECK(b >= 1, "xs must hold at least one candidate set");
+  TORCH_CHECK(q >= 1 && q <= kQeiMaxParallel, "set-PE scorer supports ",
+              "1 <= q <= ", kQeiMaxParallel, ", got q = ", q);
+  TORCH_CHECK(d <= 512, "set-PE scorer supports D <= 512, got ", d);
+  post_x = check_f32(post_x, "post_x");
+  post_alpha = check_f32(post_alpha, "post_alpha");
+  post_kinv = check_f32(post_kinv, "post_kinv");
+  all_x = check_f32(all_x, "all_x");
+  all_kinv = check_f32(all_kinv, "all_kinv");
+  lengthscales = check_f32(lengthscales, "lengthscales");
+  auto flat = xs.view({b * q, d});
+  check_scorer_args(flat, post_x, lengthscales, post_alpha, post_kinv,
+                    onehot);
+  TORCH_CHECK(all_x.dim() == 2 && all_x.size(1) == d,
+              "all_x must have xs's ", d, " columns");
+  const int64_t n = post_x.size(0), n_all = all_x.size(0);
+  TORCH_CHECK(all_kinv.dim() == 2 && all_kinv.size(0) == n_all &&
+              all_kinv.size(1) == n_all, "all_kinv must be (", n_all, ", ",
+              n_all, ")");
+  TORCH_CHECK(b * q * std::max<int64_t>(std::max(n, n_all), q) <
+              (int64_t{1} << 31), "set-PE scorer workspace too large");
+  // (mean, sd) of every member under the completed-trials posterior.
+  auto explore = posterior_mean_std(flat, post_x, lengthscales, amplitude,
+                                    post_mean_c, post_alpha, post_kinv,
+                                    onehot);
+  // Joint covariance under the completed + pending posterior (only the
+  // variance is used: alpha = 0), and every member's distance to all_x.
+  auto j = qei_joint_impl(xs, all_x, lengthscales, amplitude, 0.0,
+                          torch::zeros({n_all}, xs.options()), all_kinv,
+                          onehot);
+  return setpe_tail_impl(j.cov, explore[0], explore[1], j.dist_ws,
+                         1e-10 * amplitude * amplitude, threshold,
+                         explore_coef, penalty_coef, tr_radius);
+}
+
 torch::Tensor hv_scalarize_tr(
     torch::Tensor means, torch::Tensor sds, torch::Tensor weights,
     c10::optional<torch::Tensor> ref, c10::optional<torch::Tensor> dist,
@@ -1501,6 +1607,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "diagonal fallback + max-improvement, no trust region (gfx950)");
   m.def("qei_set_scores", &qei_set_scores,
         "Fused Monte-Carlo qEI set scorer + trust region by member 0, "
+        "stream-capturable (gfx950)");
+  m.def("setpe_scores_from_cov", &setpe_scores_from_cov,
+        "Set-PE tail: logdet of (cov + jitter I) by a one-wave Cholesky, "
+        "-inf when not positive definite, + promising-region penalty + "
+        "per-member trust region (gfx950)");
+  m.def("setpe_set_scores", &setpe_set_scores,
+        "Fused GP-UCB-PE set-PE scorer: explore (mean, sd), joint "
+        "covariance under the completed + pending posterior, logdet tail; "
         "stream-capturable (gfx950)");
   m.def("eagle_suggest", &eagle_suggest,
         "Fused Eagle suggest step (gfx950)");

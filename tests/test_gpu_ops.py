@@ -32,6 +32,7 @@ def ext():
 
 
 class TestGramKernel:
+  """Early smoke checks; tests/test_gram_kernels.py holds these kernels to fp64."""
 
   @pytest.mark.parametrize('n,m,d', [(16, 16, 4), (100, 37, 20),
                                      (1000, 1000, 20), (257, 513, 51)])
@@ -777,6 +778,7 @@ class TestGPUDesignerEndToEnd:
 
 
 class TestGramBf16MFMA:
+  """Early smoke checks; tests/test_gram_kernels.py holds these kernels to fp64."""
 
   @pytest.mark.parametrize('n,m,d', [(64, 64, 20), (500, 500, 8),
                                      (257, 130, 51)])
@@ -824,6 +826,7 @@ class TestGramBf16MFMA:
 
 
 class TestGramFp8MFMA:
+  """Early smoke checks; tests/test_gram_kernels.py holds these kernels to fp64."""
 
   @pytest.mark.parametrize('n,m,d', [(128, 130, 32), (1111, 777, 90)])
   def test_fp8_lds_tiled_matches_fp64_loosely(self, ext, n, m, d):

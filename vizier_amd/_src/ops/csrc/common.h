@@ -12,6 +12,35 @@ __device__ __forceinline__ float matern52_of_d2(float d2) {
   return (1.0f + sr + sr * sr * (1.0f / 3.0f)) * __expf(-sr);
 }
 
+// Eight OCP e4m3 bytes (byte 0 = element 0) -> eight bf16, exactly: e4m3's
+// four significant bits and its exponent range fit in bf16, so the high
+// half of the fp32 image IS the value. The fp8 grams feed these to the bf16
+// MFMA (same rate as the non-scaled fp8 one on gfx950): the fp8 MFMA sums
+// its 32 products in a truncating internal format, measured up to 2^-12.4
+// of the largest product per K-step low, which put coincident rows at
+// d^2 ~ 3e-5 instead of 0. bf16 x bf16 products of these values are exact
+// in fp32 and the bf16 MFMA accumulates them to fp32 accuracy.
+typedef __attribute__((ext_vector_type(8))) short vz_bf16x8;
+typedef __attribute__((ext_vector_type(2))) float vz_f32x2;
+
+__device__ __forceinline__ vz_bf16x8 vz_e4m3x8_to_bf16x8(long q) {
+  const int w[2] = {(int)q, (int)(q >> 32)};
+  union {
+    unsigned int u[4];
+    vz_bf16x8 v;
+  } out;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const vz_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
+    const vz_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+    out.u[2 * i] = (__float_as_uint(lo.x) >> 16) |
+                   (__float_as_uint(lo.y) & 0xffff0000u);
+    out.u[2 * i + 1] = (__float_as_uint(hi.x) >> 16) |
+                       (__float_as_uint(hi.y) & 0xffff0000u);
+  }
+  return out.v;
+}
+
 // Wave-wide reductions over all 64 lanes.
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

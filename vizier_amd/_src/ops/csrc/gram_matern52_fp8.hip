@@ -1,10 +1,13 @@
 // fp8 (OCP e4m3) MFMA Matern-5/2 Gram kernel for gfx950 (config 5).
 //
-// Same tile structure as gram_matern52_bf16.hip but the cross-term GEMM
-// uses __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8 (8 fp8 per lane,
-// packed as i64). Inputs are pre-scaled by 1/s on the host so |z| stays
-// well inside e4m3 range; the kernel multiplies the dot product back by
-// s^2. Norms come from the fp8-rounded values (exact rounded distance).
+// Same tile structure as gram_matern52_bf16.hip with fp8 operands (8 per
+// lane, packed as i64): half the operand bytes of bf16. Each K-step decodes
+// them to bf16 in registers (exact) and runs the bf16 MFMA, which on gfx950
+// has the rate of the non-scaled fp8 MFMA but accumulates to fp32 accuracy;
+// the fp8 MFMA does not (common.h, vz_e4m3x8_to_bf16x8). Inputs are
+// pre-scaled by 1/s on the host so |z| stays well inside e4m3 range; the
+// kernel multiplies the dot product back by s^2. Norms come from the
+// fp8-rounded values (exact rounded distance).
 //
 // NOTE: gfx950 uses OCP e4m3fn (not MI300X fnuz) — torch's
 // float8_e4m3fn matches (guide §4).
@@ -47,7 +50,8 @@ gram_matern52_fp8_kernel(const unsigned char* __restrict__ z1,  // (N, Dp)
         z1 + (long)a_row * dp + k0 + k_base);
     const long b = *reinterpret_cast<const long*>(
         z2 + (long)b_col * dp + k0 + k_base);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        vz_e4m3x8_to_bf16x8(a), vz_e4m3x8_to_bf16x8(b), acc, 0, 0, 0);
   }
 
 #pragma unroll

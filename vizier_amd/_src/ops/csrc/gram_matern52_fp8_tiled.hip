@@ -1,11 +1,13 @@
 // LDS-tiled fp8 (OCP e4m3) MFMA Matern-5/2 Gram kernel for gfx950.
 //
-// The 128x128 tile structure of gram_matern52_bf16_tiled.hip with the
-// fp8 MFMA (__builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8, i64-packed
-// operands): one staging pass fills both 128x32 fp8 tiles (4 KiB each)
-// via global_load_lds width-16; each wave does 8 x ds_read_b64 +
-// 16 MFMAs per K-step. Host pre-scales inputs by 1/s (e4m3 range);
-// the epilogue multiplies the dot back by s^2. gfx950 is OCP e4m3fn.
+// The 128x128 tile structure of gram_matern52_bf16_tiled.hip with fp8
+// operands (i64-packed): one staging pass fills both 128x32 fp8 tiles
+// (4 KiB each) via global_load_lds width-16; each wave does 8 x
+// ds_read_b64, decodes the 8 fragments to bf16 in registers (exact) and
+// runs 16 bf16 MFMAs per K-step, as the strip kernel does and for the same
+// reason (common.h, vz_e4m3x8_to_bf16x8). Host pre-scales inputs by 1/s
+// (e4m3 range); the epilogue multiplies the dot back by s^2. gfx950 is OCP
+// e4m3fn.
 
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -74,20 +76,22 @@ gram_matern52_fp8_tiled_kernel(
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
 
-    long aF[4], bF[4];
+    vz_bf16x8 aF[4], bF[4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       const int arow = wr * 64 + f * 16 + (lane & 15);
       const int brow = wc * 64 + f * 16 + (lane & 15);
       const int kb = (lane >> 4) * 8;
-      aF[f] = *reinterpret_cast<const long*>(ldsA + arow * BK + kb);
-      bF[f] = *reinterpret_cast<const long*>(ldsB + brow * BK + kb);
+      aF[f] = vz_e4m3x8_to_bf16x8(
+          *reinterpret_cast<const long*>(ldsA + arow * BK + kb));
+      bF[f] = vz_e4m3x8_to_bf16x8(
+          *reinterpret_cast<const long*>(ldsB + brow * BK + kb));
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             aF[i], bF[j], acc[i][j], 0, 0, 0);
     __syncthreads();
   }

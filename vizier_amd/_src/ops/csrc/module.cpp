@@ -259,16 +259,37 @@ void check_cached_operands(const torch::Tensor& z2, const torch::Tensor& n2,
               " elements, got ", n2.numel());
 }
 
+// Shape checks shared by the gram bindings: the kernels index x1, x2 and
+// the lengthscales by (n, m, d) taken from x1 and x2 alone, so the
+// operands must agree BEFORE any size() read past dim() or any launch.
+void check_gram_args(const torch::Tensor& x1, const torch::Tensor& x2,
+                     const torch::Tensor& lengthscales) {
+  TORCH_CHECK(x1.dim() == 2 && x2.dim() == 2,
+              "x1 and x2 must be 2-D, got ", x1.dim(), "-D and ",
+              x2.dim(), "-D");
+  const int64_t d = x1.size(1);
+  TORCH_CHECK(x2.size(1) == d, "x2 must have x1's ", d, " columns, got ",
+              x2.size(1));
+  TORCH_CHECK(lengthscales.numel() == d, "lengthscales must have ", d,
+              " elements, got ", lengthscales.numel());
+}
+
 torch::Tensor gram_matern52(torch::Tensor x1, torch::Tensor x2,
                             torch::Tensor lengthscales, double amplitude) {
   x1 = check_f32(x1, "x1");
   x2 = check_f32(x2, "x2");
   lengthscales = check_f32(lengthscales, "lengthscales");
+  check_gram_args(x1, x2, lengthscales);
+  // The kernel indexes out[row * m + col] and x[row * d + c] in int.
+  TORCH_CHECK(x1.size(0) * x2.size(0) < (int64_t(1) << 31) &&
+              x1.numel() < (int64_t(1) << 31) &&
+              x2.numel() < (int64_t(1) << 31),
+              "gram_matern52 supports fewer than 2^31 elements in x1, x2 "
+              "and the (", x1.size(0), ", ", x2.size(0), ") output");
   const int n = x1.size(0), m = x2.size(0), d = x1.size(1);
-  TORCH_CHECK(x2.size(1) == d && lengthscales.numel() == d,
-              "dimension mismatch");
-  auto inv_ls = 1.0f / lengthscales;
   auto out = torch::empty({n, m}, x1.options());
+  if (n == 0 || m == 0) return out;
+  auto inv_ls = 1.0f / lengthscales;
   const int sym = (x1.data_ptr() == x2.data_ptr() && n == m) ? 1 : 0;
   launch_gram_matern52(x1.data_ptr<float>(), x2.data_ptr<float>(),
                        inv_ls.data_ptr<float>(), out.data_ptr<float>(), n,
@@ -287,12 +308,18 @@ std::vector<torch::Tensor> gram_matern52_batched(
   lengthscales = check_f32(lengthscales, "lengthscales");
   amplitude = check_f32(amplitude, "amplitude");
   noise = check_f32(noise, "noise");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D, got ", x.dim(), "-D");
+  TORCH_CHECK(lengthscales.dim() == 2 &&
+              lengthscales.size(1) == x.size(1),
+              "lengthscales must be (R, D) with x's D");
   const int n = x.size(0), d = x.size(1);
   const int r = lengthscales.size(0);
-  TORCH_CHECK(lengthscales.dim() == 2 && lengthscales.size(1) == d,
-              "lengthscales must be (R, D)");
   TORCH_CHECK(amplitude.numel() == r && noise.numel() == r,
               "amplitude/noise must be (R,)");
+  // The kernel indexes x[row * d + c] in int and R rides on gridDim.y.
+  TORCH_CHECK(x.numel() < (int64_t(1) << 31) && r <= 65535,
+              "gram_matern52_batched supports fewer than 2^31 elements in "
+              "x and R <= 65535");
   auto inv_ls = (1.0f / lengthscales).contiguous();
   auto amp2 = (amplitude * amplitude).contiguous();
   auto K = torch::empty({r, n, n}, x.options());
@@ -301,6 +328,10 @@ std::vector<torch::Tensor> gram_matern52_batched(
   if (want_grad_factor) {
     G = torch::empty({r, n, n}, x.options());
     gptr = G.data_ptr<float>();
+  }
+  if (n == 0 || r == 0) {
+    if (want_grad_factor) return {K, G};
+    return {K};
   }
   launch_gram_matern52_batched(
       x.data_ptr<float>(), inv_ls.data_ptr<float>(),
@@ -316,11 +347,15 @@ torch::Tensor gram_matern52_bf16_impl(torch::Tensor x1, torch::Tensor x2,
   x1 = check_f32(x1, "x1");
   x2 = check_f32(x2, "x2");
   lengthscales = check_f32(lengthscales, "lengthscales");
+  check_gram_args(x1, x2, lengthscales);
   const int n = x1.size(0), m = x2.size(0), d = x1.size(1);
-  TORCH_CHECK(x2.size(1) == d && lengthscales.numel() == d,
-              "dimension mismatch");
+  if (n == 0 || m == 0) return torch::empty({n, m}, x1.options());
   auto z1 = x1 / lengthscales;
-  auto z2 = (x1.data_ptr() == x2.data_ptr()) ? z1 : x2 / lengthscales;
+  // Same pointer is the same operand only when the row counts agree too:
+  // x[:1] and x share a pointer, and a (1, d) z1 would be broadcast into
+  // every row of z2b below.
+  auto z2 = (x1.data_ptr() == x2.data_ptr() && n == m) ? z1
+                                                       : x2 / lengthscales;
   const int dp = (d + 31) / 32 * 32;
   auto z1b = torch::zeros({n, dp},
                           x1.options().dtype(torch::kBFloat16));
@@ -350,7 +385,8 @@ torch::Tensor gram_matern52_bf16(torch::Tensor x1, torch::Tensor x2,
                                  double amplitude) {
   // LDS-tiled MFMA path once both dims fill 128x128 tiles; the
   // register-direct strip kernel has less overhead for small grams.
-  const bool tiled = x1.size(0) >= 512 && x2.size(0) >= 512;
+  const bool tiled = x1.dim() == 2 && x2.dim() == 2 &&
+                     x1.size(0) >= 512 && x2.size(0) >= 512;
   return gram_matern52_bf16_impl(x1, x2, lengthscales, amplitude, tiled);
 }
 
@@ -396,9 +432,13 @@ torch::Tensor gram_matern52_fp8_impl(torch::Tensor x1, torch::Tensor x2,
   x1 = check_f32(x1, "x1");
   x2 = check_f32(x2, "x2");
   lengthscales = check_f32(lengthscales, "lengthscales");
+  check_gram_args(x1, x2, lengthscales);
   const int n = x1.size(0), m = x2.size(0), d = x1.size(1);
+  if (n == 0 || m == 0) return torch::empty({n, m}, x1.options());
   auto z1 = x1 / lengthscales;
-  auto z2 = (x1.data_ptr() == x2.data_ptr()) ? z1 : x2 / lengthscales;
+  // As in the bf16 binding: alias only when the row counts agree.
+  auto z2 = (x1.data_ptr() == x2.data_ptr() && n == m) ? z1
+                                                       : x2 / lengthscales;
   // Pre-scale into comfortable e4m3 range (|z|/s <= ~8).
   double s = std::max(z1.abs().max().item<double>(),
                       z2.abs().max().item<double>()) / 8.0;
@@ -431,7 +471,8 @@ torch::Tensor gram_matern52_fp8_impl(torch::Tensor x1, torch::Tensor x2,
 torch::Tensor gram_matern52_fp8(torch::Tensor x1, torch::Tensor x2,
                                 torch::Tensor lengthscales,
                                 double amplitude) {
-  const bool tiled = x1.size(0) >= 512 && x2.size(0) >= 512;
+  const bool tiled = x1.dim() == 2 && x2.dim() == 2 &&
+                     x1.size(0) >= 512 && x2.size(0) >= 512;
   return gram_matern52_fp8_impl(x1, x2, lengthscales, amplitude, tiled);
 }
 
@@ -504,14 +545,27 @@ torch::Tensor gram_matern52_fp8_pre(
   TORCH_CHECK(z1q.scalar_type() == torch::kFloat8_e4m3fn &&
               z2q.scalar_type() == torch::kFloat8_e4m3fn,
               "z1q/z2q must be float8_e4m3fn");
+  TORCH_CHECK(z1q.is_cuda() && z2q.is_cuda(),
+              "z1q/z2q must be GPU tensors");
+  TORCH_CHECK(z1q.dim() == 2 && z2q.dim() == 2,
+              "z1q and z2q must be 2-D, got ", z1q.dim(), "-D and ",
+              z2q.dim(), "-D");
   z1q = z1q.contiguous();
   z2q = z2q.contiguous();
   n1 = check_f32(n1, "n1");
   n2 = check_f32(n2, "n2");
   const int n = z1q.size(0), m = z2q.size(0), dp = z1q.size(1);
-  TORCH_CHECK(z2q.size(1) == dp && dp % 32 == 0, "dp mismatch");
+  TORCH_CHECK(z2q.size(1) == dp && dp % 32 == 0,
+              "z1q and z2q must share a column count that is a multiple "
+              "of 32, got ", dp, " and ", z2q.size(1));
+  // The kernel indexes n1 and n2 by n and m.
+  TORCH_CHECK(n1.numel() == n, "n1 must have ", n, " elements, got ",
+              n1.numel());
+  TORCH_CHECK(n2.numel() == m, "n2 must have ", m, " elements, got ",
+              n2.numel());
   auto out = torch::empty({n, m},
                           n1.options().dtype(torch::kFloat32));
+  if (n == 0 || m == 0) return out;
   const bool tiled = n >= 512 && m >= 512;
   auto launch = tiled ? launch_gram_matern52_fp8_tiled
                       : launch_gram_matern52_fp8;

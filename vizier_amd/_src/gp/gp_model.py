@@ -192,11 +192,33 @@ def _use_custom_trsv(K: torch.Tensor) -> bool:
           K.shape[-1] <= 1200 and ops.extension_available())
 
 
+def _trsv_variant() -> int:
+  """Kernel behind ext.batched_trsv_lower: 0 = the pipelined
+  register-resident solve (default), 1 = the LDS-staged solve it
+  replaced (VIZIER_AMD_TRSV=v1). Bit-identical results; read on every
+  call so one process can time both."""
+  return 1 if os.environ.get('VIZIER_AMD_TRSV') == 'v1' else 0
+
+
 def nll_values_with_chol(raw: torch.Tensor, x: torch.Tensor,
                          y: torch.Tensor):
   """Batched NLL that also returns its Cholesky factors.
 
-  Returns (nll (R,), L (R, N, N), info (R,) int). The factors let the
+  Returns (nll (R,), L (R, N, N), info (R,) int); see
+  `nll_values_with_chol_z` for the variant that also hands over the
+  solve."""
+  nll, L, info, _ = nll_values_with_chol_z(raw, x, y)
+  return nll, L, info
+
+
+def nll_values_with_chol_z(raw: torch.Tensor, x: torch.Tensor,
+                           y: torch.Tensor):
+  """Batched NLL that also returns its Cholesky factors and the solve.
+
+  Returns (nll (R,), L (R, N, N), info (R,) int, z). z = L^-1 (y - mean)
+  is (R, N) from the HIP solve and (R, N, 1) from torch's, and goes with
+  the factor: `nll_value_and_grad(chol_hint=(L, info, z))` would solve
+  the same system on the same L again. The factors let the
   L-BFGS line search hand the ACCEPTED candidate's factorization to
   the gradient evaluation (lbfgs.py `ladder_fn`), skipping one full
   batched potrf per iteration — x_new is bit-identical to the selected
@@ -224,7 +246,8 @@ def nll_values_with_chol(raw: torch.Tensor, x: torch.Tensor,
     ext = ops.require_ext()
     L, info = ext.batched_potrf(K.contiguous())
     z = ext.batched_trsv_lower(
-        L, resid.squeeze(-1).expand(K.shape[0], n).contiguous())
+        L, resid.squeeze(-1).expand(K.shape[0], n).contiguous(),
+        _trsv_variant())
     quad = (z * z).sum(dim=-1)
   else:
     L, info = safe_cholesky_ex(K)
@@ -232,7 +255,8 @@ def nll_values_with_chol(raw: torch.Tensor, x: torch.Tensor,
       ext = ops.require_ext()
       z = ext.batched_trsv_lower(
           L.contiguous(),
-          resid.squeeze(-1).expand(K.shape[0], n).contiguous())
+          resid.squeeze(-1).expand(K.shape[0], n).contiguous(),
+          _trsv_variant())
       quad = (z * z).sum(dim=-1)
     else:
       # quad = r^T K^-1 r = ||L^-1 r||^2: ONE triangular solve instead
@@ -248,7 +272,7 @@ def nll_values_with_chol(raw: torch.Tensor, x: torch.Tensor,
   nll = nll + 0.01 * (raw * raw).sum(-1)
   # Failed factorizations get +inf so the optimizer backs off.
   nll = torch.where(info == 0, nll, torch.full_like(nll, float('inf')))
-  return nll, L, info
+  return nll, L, info, z
 
 
 def negative_log_marginal_likelihood(raw: torch.Tensor, x: torch.Tensor,
@@ -307,13 +331,24 @@ def nll_value_and_grad(raw: torch.Tensor, x: torch.Tensor,
   if chol_hint is not None:
     # The line-search ladder already factored K at these exact raw
     # values (bit-identical x_new); reuse its (L, info) and skip the
-    # batched potrf entirely.
-    L, info = chol_hint
+    # batched potrf entirely. A three-member hint also carries the
+    # ladder's z = L^-1 resid. Where both sides run the HIP solve it is
+    # the same kernel on the same L and the same resid, so the same bits
+    # as solving again here, and the solve is skipped. torch's solve
+    # rounds differently for a differently strided L (the ladder solves
+    # on cholesky_ex's output, this path on a gathered copy), so there
+    # z is not taken over.
+    L, info = chol_hint[0], chol_hint[1]
+    z_hint = chol_hint[2] if len(chol_hint) > 2 else None
     L = L.contiguous()
     if _use_custom_chol(K) or _use_custom_trsv(K):
-      ext = ops.require_ext()
-      zs = ext.batched_trsv_lower(
-          L, resid.squeeze(-1).expand(K.shape[0], n).contiguous())
+      if z_hint is not None and z_hint.dim() == 2:
+        zs = z_hint
+      else:
+        ext = ops.require_ext()
+        zs = ext.batched_trsv_lower(
+            L, resid.squeeze(-1).expand(K.shape[0], n).contiguous(),
+            _trsv_variant())
       quad = (zs * zs).sum(dim=-1)
     else:
       zsol = torch.linalg.solve_triangular(L, resid, upper=False)
@@ -326,7 +361,8 @@ def nll_value_and_grad(raw: torch.Tensor, x: torch.Tensor,
     ext = ops.require_ext()
     L, info = ext.batched_potrf(K.contiguous())
     zs = ext.batched_trsv_lower(
-        L, resid.squeeze(-1).expand(K.shape[0], n).contiguous())
+        L, resid.squeeze(-1).expand(K.shape[0], n).contiguous(),
+        _trsv_variant())
     quad = (zs * zs).sum(dim=-1)
   else:
     L, info = safe_cholesky_ex(K)
@@ -539,16 +575,17 @@ def train_gp(x: torch.Tensor, y: torch.Tensor, *,
     # ROCm 7.2 (even unbatched), so huge studies cannot autograd the
     # NLL. Fit with ANALYTIC gradients instead (forward-only solves,
     # verified against autograd to 1e-9 in tests/test_gp_core.py).
-    # Ladder-cache: the line search returns its (L, info) per trial so
-    # the gradient eval at the accepted point (bit-identical raw)
-    # skips one full batched potrf per iteration. Gated on cache size
+    # Ladder-cache: the line search returns its (L, info, z) per trial
+    # so the gradient eval at the accepted point (bit-identical raw)
+    # skips one full batched potrf, and on the HIP solve also the
+    # forward substitution, per iteration. Gated on cache size
     # (the (S*R, N, N) factors are ~6 GB at config-4 scale).
     r_ladder = raw0.shape[0] * 4  # ls_steps ladder width
     ladder = None
     if r_ladder * n * n * 4 <= (1 << 30):
       def ladder(raw):
-        nll_v, L, information = nll_values_with_chol(raw, x, y)
-        return nll_v, (L, information)
+        nll_v, L, information, z = nll_values_with_chol_z(raw, x, y)
+        return nll_v, (L, information, z)
     best_raw, best_f = lbfgs.minimize_batched(
         loss_fn, raw0, max_iters=max_iters, check_every=5,
         value_and_grad_fn=lambda raw, hint=None: nll_value_and_grad(

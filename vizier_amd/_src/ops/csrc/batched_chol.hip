@@ -9,9 +9,22 @@
 // wave-synchronous blocked forward substitution. Forward-only: the
 // autograd value_and_grad path keeps torch's factorization; the
 // line-search (torch.no_grad) calls these.
+//
+// Forward substitution, two kernels with bit-identical results
+// (tests/test_trsv_variants.py; launch_batched_trsv_lower picks):
+//   - batched_trsv_lower_pipe_kernel (default, N <= 1280): every row's
+//     accumulator and its L columns stay in registers, the diagonal block
+//     is fetched one panel ahead and the panel's columns load while the
+//     32-step chain runs, one block barrier per panel;
+//   - batched_trsv_lower_kernel (variant 1, and N > 1280): stages the
+//     panel's columns through LDS and read-modify-writes rhs in global
+//     memory, two barriers per 256-row chunk, nothing prefetched.
+// Measured at 16 x 1000 x 1000 (profiles/bench_resident_trsv.md): 632 ->
+// 146 us per call, the b.clone() of the binding included.
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 
 #include "common.h"
@@ -186,6 +199,166 @@ batched_trsv_lower_kernel(const float* __restrict__ L,  // (R, N, N)
       }
       __syncthreads();
     }
+  }
+}
+
+// -- Pipelined forward substitution (default) ----------------------------
+//
+// Same arithmetic as batched_trsv_lower_kernel, row by row:
+//   acc = b[i]; acc = fmaf(-L[i][j], z[j], acc) for j = 0 .. i-1 in column
+//   order; z[i] = acc / L[i][i]
+// so z is bit-identical. What changes is where the operands wait:
+//   - thread t owns rows t, t + 256, ... (RPT of them) and keeps their
+//     accumulators in registers for the whole solve: no read-modify-write
+//     of rhs in global memory;
+//   - it reads L[i][k0 .. k0+31] (one 128-byte line) straight into
+//     registers, as float4 when VEC (n % 4 == 0, 16-byte aligned base),
+//     and only for rows below the panel: no LDS transpose, two block
+//     barriers per panel become one;
+//   - the 32 rows of diagonal block k are rows of 32 consecutive threads
+//     (256 is a multiple of 32): half of wave (k % 8) / 2. That half-wave
+//     already holds their accumulators, so it runs the 32-step chain in
+//     place, broadcasting z[j] with v_readlane;
+//   - the diagonal block of panel k + 1 is fetched one panel ahead, and
+//     the other three waves' columns of panel k are in flight while the
+//     chain of panel k runs, so the chain itself never waits on memory.
+// What is left per panel (146 us / 32 at N = 1000) is the chain, of the
+// order of 1.7 us of dependent divide / readlane / fma, the chain wave's
+// own column loads, which land after it, and the address-per-lane loads
+// themselves: one float4 per lane per line, 8 instructions per row.
+// The strict upper triangle of a diagonal block is loaded with its row but
+// only ever selected away: lane l divides by dg[l] and multiplies dg[j] for
+// j < l.
+#define TRSV_PIPE_MAX_RPT 5
+
+template <bool VEC>
+__device__ __forceinline__ void trsv_load_row(const float* __restrict__ p,
+                                              int ncols, float out[NB]) {
+  if (VEC) {
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (4 * q < ncols) v = *reinterpret_cast<const float4*>(p + 4 * q);
+      out[4 * q] = v.x;
+      out[4 * q + 1] = v.y;
+      out[4 * q + 2] = v.z;
+      out[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) out[c] = (c < ncols) ? p[c] : 0.0f;
+  }
+}
+
+template <int RPT, bool VEC>
+__global__ __launch_bounds__(CB) void
+batched_trsv_lower_pipe_kernel(const float* __restrict__ L,  // (R, N, N)
+                               float* __restrict__ b,        // (R, N)
+                               int r_count, int n) {
+  __shared__ float zseg[2][NB];  // double-buffered: one barrier per panel
+  const int r = blockIdx.x;
+  if (r >= r_count) return;
+  const float* M = L + (long)r * n * n;
+  float* rhs = b + (long)r * n;
+  const int tid = threadIdx.x;
+  const int lane = tid % WAVE_SIZE;
+  const int wave = tid / WAVE_SIZE;
+  const int l = tid % NB;    // row of a diagonal block this thread owns
+  const int blk = tid / NB;  // ... in the panels with k % 8 == blk
+
+  float acc[RPT];
+  float cur[RPT][NB];
+#pragma unroll
+  for (int s = 0; s < RPT; ++s) {
+    const int i = tid + s * CB;
+    acc[s] = (i < n) ? rhs[i] : 0.0f;
+#pragma unroll
+    for (int c = 0; c < NB; ++c) cur[s][c] = 0.0f;
+  }
+  float dg[NB], dgn[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) dg[c] = dgn[c] = 0.0f;
+  if (blk == 0 && l < n) trsv_load_row<VEC>(M + (long)l * n, min(NB, n), dg);
+
+  const int npanels = (n + NB - 1) / NB;
+  for (int k = 0; k < npanels; ++k) {
+    const int k0 = k * NB;
+    const int nb = min(NB, n - k0);
+    const int below = k0 + nb;  // < n only after a full panel
+
+    // Columns of this panel for the rows below it, and the next diagonal
+    // block: in flight while the chain runs.
+    auto issue_loads = [&]() {
+#pragma unroll
+      for (int s = 0; s < RPT; ++s) {
+        const int i = tid + s * CB;
+        if (i >= below && i < n) {
+          trsv_load_row<VEC>(M + (long)i * n + k0, NB, cur[s]);
+        }
+      }
+      const int k1 = k0 + NB;
+      if (blk == ((k + 1) & 7) && k1 + l < n) {
+        trsv_load_row<VEC>(M + (long)(k1 + l) * n + k1, min(NB, n - k1),
+                           dgn);
+      }
+    };
+    // The wave that runs the chain issues its loads after it: 64 lanes
+    // x 8 float4 per row each touch their own line, and queueing those
+    // ahead of the chain delayed it by more than the loads' latency
+    // costs afterwards (175 -> 146 us per call, 16 x 1000 x 1000).
+    const bool owner = wave == ((k & 7) >> 1);
+    if (!owner) issue_loads();
+
+    if (owner) {
+      const int h = (k & 1) * NB;  // first lane of the owning half-wave
+      const int sd = k0 / CB;      // the owners' slot of these rows
+      float myv = 0.0f;
+#pragma unroll
+      for (int s = 0; s < RPT; ++s) {
+        if (s == sd) myv = acc[s];
+      }
+      const int ll = lane - h;     // == l in the owning half, else outside
+      const bool mine = ll >= 0 && ll < nb;
+      float myz = 0.0f;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        if (j >= nb) break;
+        float zj = 0.0f;
+        if (ll == j) {
+          zj = myv / dg[j];
+          myz = zj;
+        }
+        zj = __int_as_float(
+            __builtin_amdgcn_readlane(__float_as_int(zj), h + j));
+        if (mine && ll > j) {
+          myv = fmaf(-dg[j], zj, myv);
+        }
+      }
+      if (mine) {
+        zseg[k & 1][ll] = myz;
+        rhs[k0 + ll] = myz;
+      }
+      issue_loads();
+    }
+    __syncthreads();
+
+    if (below < n) {
+      float zs[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) zs[j] = zseg[k & 1][j];
+#pragma unroll
+      for (int s = 0; s < RPT; ++s) {
+        const int i = tid + s * CB;
+        if (i >= below && i < n) {
+          float a = acc[s];
+#pragma unroll
+          for (int j = 0; j < NB; ++j) a = fmaf(-cur[s][j], zs[j], a);
+          acc[s] = a;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NB; ++c) dg[c] = dgn[c];
   }
 }
 
@@ -1099,9 +1272,37 @@ extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
                      dim3(CB), 0, stream, A, info, r, n);
 }
 
+template <int RPT>
+static void launch_trsv_pipe(const float* L, float* b, int r, int n,
+                             hipStream_t stream) {
+  const bool vec = n % 4 == 0 &&
+                   reinterpret_cast<uintptr_t>(L) % 16 == 0;
+  if (vec) {
+    hipLaunchKernelGGL((batched_trsv_lower_pipe_kernel<RPT, true>),
+                       dim3(r), dim3(CB), 0, stream, L, b, r, n);
+  } else {
+    hipLaunchKernelGGL((batched_trsv_lower_pipe_kernel<RPT, false>),
+                       dim3(r), dim3(CB), 0, stream, L, b, r, n);
+  }
+}
+
+// variant 0: pipelined register-resident solve while the rows fit
+// (N <= 256 * TRSV_PIPE_MAX_RPT = 1280), else the LDS-staged kernel.
+// variant 1: the LDS-staged kernel.
 extern "C" void launch_batched_trsv_lower(const float* L, float* b,
-                                          int r, int n,
+                                          int r, int n, int variant,
                                           hipStream_t stream) {
-  hipLaunchKernelGGL(batched_trsv_lower_kernel, dim3(r), dim3(CB), 0,
-                     stream, L, b, r, n);
+  const int rpt = (n + CB - 1) / CB;
+  if (variant == 1 || rpt > TRSV_PIPE_MAX_RPT) {
+    hipLaunchKernelGGL(batched_trsv_lower_kernel, dim3(r), dim3(CB), 0,
+                       stream, L, b, r, n);
+    return;
+  }
+  switch (rpt) {
+    case 1: launch_trsv_pipe<1>(L, b, r, n, stream); break;
+    case 2: launch_trsv_pipe<2>(L, b, r, n, stream); break;
+    case 3: launch_trsv_pipe<3>(L, b, r, n, stream); break;
+    case 4: launch_trsv_pipe<4>(L, b, r, n, stream); break;
+    default: launch_trsv_pipe<5>(L, b, r, n, stream); break;
+  }
 }

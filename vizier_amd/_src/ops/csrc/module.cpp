@@ -141,7 +141,7 @@ extern "C" int launch_batched_potrf_v5(const float* A, float* panels,
                                        int* info, unsigned int* bar,
                                        int r, int n, hipStream_t stream);
 extern "C" void launch_batched_trsv_lower(const float* L, float* b,
-                                          int r, int n,
+                                          int r, int n, int variant,
                                           hipStream_t stream);
 
 extern "C" void launch_eagle_suggest(
@@ -1197,7 +1197,12 @@ std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
   return {L, info};
 }
 
-torch::Tensor batched_trsv_lower(torch::Tensor L, torch::Tensor b) {
+// variant 0: the pipelined register-resident solve (N <= 1280; larger N
+// runs variant 1). variant 1: the LDS-staged solve. Same bits either way.
+torch::Tensor batched_trsv_lower(torch::Tensor L, torch::Tensor b,
+                                 int64_t variant) {
+  TORCH_CHECK(variant == 0 || variant == 1,
+              "batched_trsv_lower variant must be 0 or 1, got ", variant);
   L = check_f32(L, "L");
   b = check_f32(b, "b");
   TORCH_CHECK(L.dim() == 3 && L.size(1) == L.size(2) &&
@@ -1208,7 +1213,7 @@ torch::Tensor batched_trsv_lower(torch::Tensor L, torch::Tensor b) {
               L.size(0), ", N = ", L.size(1));
   auto z = b.clone();
   launch_batched_trsv_lower(L.data_ptr<float>(), z.data_ptr<float>(),
-                            (int)L.size(0), (int)L.size(1),
+                            (int)L.size(0), (int)L.size(1), (int)variant,
                             current_stream());
   return z;
 }
@@ -1640,7 +1645,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "unspecified values. info[r] is the 1-based first column whose "
         "pivot is not > 0 (zero, negative or NaN), 0 on success (gfx950)");
   m.def("batched_trsv_lower", &batched_trsv_lower,
-        "Batched forward substitution L z = b (gfx950)");
+        "Batched forward substitution L z = b (gfx950). variant 0 = "
+        "pipelined register-resident solve, 1 = LDS-staged solve; "
+        "bit-identical results",
+        py::arg("L"), py::arg("b"), py::arg("variant") = 0);
   m.def("gram_matern52_fp8_pre", &gram_matern52_fp8_pre,
         "fp8 cross-gram from pre-quantized operands (gfx950)");
   m.def("posterior_mean_std_fp8", &posterior_mean_std_fp8,

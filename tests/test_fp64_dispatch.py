@@ -77,6 +77,17 @@ def test_megakernel_is_fp32_only(monkeypatch):
   assert not opt._megakernel_applicable(score_fn)
 
 
+def test_megakernel_is_limited_to_512_continuous_features(monkeypatch):
+  """The kernel keeps one candidate in xq_lds[512]; a wider space takes
+  the hipGraph path."""
+  monkeypatch.delenv('VIZIER_AMD_MEGAKERNEL', raising=False)
+  opt, score_fn = _megakernel_stub(torch.float32)
+  score_fn.scoring.posterior.x.shape = (64, 512)
+  assert opt._megakernel_applicable(score_fn)
+  score_fn.scoring.posterior.x.shape = (64, 513)
+  assert not opt._megakernel_applicable(score_fn)
+
+
 def test_splitmix64_oracle_known_values():
   # vz_splitmix64(z) = mix(z + 0x9e3779b97f4a7c15) with the multipliers
   # 0xbf58476d1ce4e5b9 / 0x94d049bb133111eb and shifts 30 / 27 / 31 of

@@ -118,13 +118,18 @@ class VectorizedOptimizer:
         rewards=top.values)
 
   def _megakernel_applicable(self, score_fn: ScoreFn) -> bool:
-    """Persistent-megakernel preconditions: GPU ext, continuous-only,
-    q == 1, and a fused-able ScoringFunction (same conditions as the
-    chunked HIP scorer fast path)."""
+    """Persistent-megakernel preconditions: GPU ext, continuous-only
+    with at most 512 features (the kernel's xq_lds), q == 1, and a
+    fused-able ScoringFunction (same conditions as the chunked HIP
+    scorer fast path)."""
     import os
     if os.environ.get('VIZIER_AMD_MEGAKERNEL', '1') != '1':
       # Default ON: 68 us/iteration vs 85 for the hipGraph replay
-      # (profiles/megatime3.log), bit-identical results (GPU test).
+      # (profiles/megatime3.log). Bitwise equal to the step kernels of
+      # the hipGraph path for N < 4096; for 4096 <= N <= 8192 the
+      # standalone scorer takes its SGEMM quadform, so the two paths
+      # agree to the fp64-oracle tolerance only
+      # (tests/test_sweep_kernel.py).
       # Set VIZIER_AMD_MEGAKERNEL=0 to force the hipGraph path.
       return False
     strategy = self.strategy
@@ -143,7 +148,10 @@ class VectorizedOptimizer:
             getattr(scoring, 'gram_dtype', 'fp32') == 'fp32' and
             post.K_inv is not None and post.x.is_cuda and
             strategy.pool_size <= 128 and strategy.batch_size <= 32
-            and post.x.shape[0] <= 8192)
+            and post.x.shape[0] <= 8192
+            # The kernel's dc is x's width (continuous-only, identity
+            # codec: strategy.n_continuous); xq_lds holds 512.
+            and post.x.shape[1] <= 512)
 
   def _optimize_megakernel(self, score_fn: ScoreFn, count: int, state,
                            iterations: int) -> VectorizedStrategyResults:
@@ -152,8 +160,11 @@ class VectorizedOptimizer:
     with grid-wide barriers, zero per-iteration dispatches. The
     initialization phase (+2 steady iterations, aligning the device
     counter) runs eagerly like the hipGraph path; the device phases
-    replicate the standalone kernels verbatim, so results are
-    bit-identical to the hipGraph path for the same seeds."""
+    replicate the standalone kernels verbatim, so for N < 4096 results
+    are bit-identical to the hipGraph path for the same seeds. For
+    4096 <= N <= 8192 the standalone scorer switches to its SGEMM
+    quadform while the sweep keeps the 64x64 tiles: there the two paths
+    agree to the fp64-oracle tolerance, not bitwise."""
     import torch as _torch
 
     strategy = self.strategy

@@ -26,13 +26,22 @@
 // config); the optimizer falls back to the hipGraph path otherwise.
 //
 // Determinism: phases replicate the standalone kernels VERBATIM (same
-// counter-based RNG streams, same NCHUNK quadform partition, same
-// block-reduce orders), so the sweep is BIT-IDENTICAL to the hipGraph
-// path for the same seeds (asserted by tests/test_gpu_ops.py).
+// counter-based RNG streams, same 64x64 tile quadform and partial
+// order, same block-reduce orders), so for N < 4096 the sweep is
+// BIT-IDENTICAL to the step kernels of the hipGraph path for the same
+// seeds: the whole pool state, asserted by tests/test_sweep_kernel.py
+// and tests/test_gpu_ops.py. For 4096 <= N <= 8192 the standalone
+// scorer switches to a row-split k-vector kernel plus one SGEMM
+// (module.cpp, gemm_n_threshold) while the sweep keeps this file's
+// k-vector loop and the tiles, so the two paths sum in different orders
+// and agree only to the fp64-oracle tolerance; that range is held to
+// the fp64 oracle phase by phase (tests/test_sweep_kernel.py).
 //
 // Deadlock safety: every phase is a grid-stride loop (any grid size is
-// correct); the launcher clamps the grid to the cooperative occupancy
-// limit, and cooperative launch guarantees co-residency.
+// correct: grids of 1, 7 and 200 workgroups are run by
+// tests/test_sweep_kernel.py); the launcher clamps the grid to the
+// cooperative occupancy limit, and cooperative launch guarantees
+// co-residency.
 
 #include <hip/hip_runtime.h>
 
@@ -290,8 +299,9 @@ eagle_sweep_kernel(
     // ---- Phase B: K^-1 quadform (64x64 tiles, Kinv read ONCE) ----
     // Shared template with the standalone chunked scorer
     // (vz_quadform_tile in common.h): identical float-op order keeps
-    // the megakernel bit-identical to the hipGraph path. var_ws layout
-    // is (B, T+1): T tile partials + the reduced quadform.
+    // the megakernel bit-identical to the hipGraph path wherever that
+    // path takes the tile quadform too (N < 4096). var_ws layout is
+    // (B, T+1): T tile partials + the reduced quadform.
     {
       const int tiles_n = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
       const int total_tiles = tiles_n * tiles_n;

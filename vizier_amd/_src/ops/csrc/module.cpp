@@ -1425,23 +1425,66 @@ int64_t eagle_sweep(
     int64_t seed_suggest, int64_t seed_update, double amp2,
     double mean_c, int64_t acq, double coef, double best_value,
     double tr_radius) {
-  pool_cont = check_f32(pool_cont, "pool_cont");
-  rewards = check_f32(rewards, "rewards");
-  perturbations = check_f32(perturbations, "perturbations");
+  // Every check throws before anything is launched. The state and the
+  // workspaces are written in place, so they are never copied: a
+  // contiguous image would take the update and the caller's tensor none.
+  check_inplace(pool_cont, torch::kFloat32, "pool_cont");
+  check_inplace(rewards, torch::kFloat32, "rewards");
+  check_inplace(perturbations, torch::kFloat32, "perturbations");
+  check_inplace(best_reward, torch::kFloat32, "best_reward");
+  check_inplace(iter_counter, torch::kInt64, "iter_counter");
+  check_inplace(barrier_buf, torch::kInt32, "barrier_buf");
+  check_inplace(out_cont, torch::kFloat32, "out_cont");
+  check_inplace(k_ws, torch::kFloat32, "k_ws");
+  check_inplace(mu_ws, torch::kFloat32, "mu_ws");
+  check_inplace(dist_ws, torch::kFloat32, "dist_ws");
+  check_inplace(var_ws, torch::kFloat32, "var_ws");
   x = check_f32(x, "x");
   inv_ls = check_f32(inv_ls, "inv_ls");
   alpha = check_f32(alpha, "alpha");
   kinv = check_f32(kinv, "kinv");
-  TORCH_CHECK(barrier_buf.scalar_type() == torch::kInt32 &&
-              barrier_buf.numel() >= 2, "barrier_buf must be int32 (2,)");
-  const int dc = x.size(1);
-  const int n = x.size(0);
+  TORCH_CHECK(barrier_buf.numel() >= 2, "barrier_buf must be int32 (2,)");
+  TORCH_CHECK(x.dim() == 2, "x must be (N, Dc)");
+  const int64_t dc64 = x.size(1), n64 = x.size(0);
+  // xq_lds[512] in the kernel is indexed by j < dc.
+  TORCH_CHECK(dc64 >= 1 && dc64 <= 512,
+              "eagle_sweep supports 1 <= Dc <= 512, got ", dc64);
+  TORCH_CHECK(n64 >= 1 && n64 <= 8192,
+              "eagle_sweep supports 1 <= N <= 8192, got ", n64);
+  TORCH_CHECK(pool_size >= 1 && pool_size <= 128,
+              "eagle_sweep supports 1 <= pool <= 128, got ", pool_size);
+  TORCH_CHECK(batch_size >= 1 && batch_size <= 32,
+              "eagle_sweep tile quadform supports 1 <= batch <= 32, got ",
+              batch_size);
+  TORCH_CHECK(n_batches >= 1 && n_batches * batch_size == pool_size,
+              "pool_size must be n_batches * batch_size, got ", pool_size,
+              " != ", n_batches, " * ", batch_size);
+  TORCH_CHECK(iterations >= 0, "iterations must be >= 0, got ", iterations);
+  const int dc = (int)dc64;
+  const int n = (int)n64;
   TORCH_CHECK(pool_cont.numel() == pool_size * dc,
               "pool/feature shape mismatch (continuous-only, q=1)");
-  TORCH_CHECK(pool_size <= 128, "eagle_sweep supports pool <= 128");
-  TORCH_CHECK(n <= 8192, "eagle_sweep supports N <= 8192");
-  TORCH_CHECK(batch_size <= 32,
-              "eagle_sweep tile quadform supports batch <= 32");
+  TORCH_CHECK(rewards.numel() == pool_size &&
+              perturbations.numel() == pool_size,
+              "rewards / perturbations must have pool_size = ", pool_size,
+              " elements");
+  TORCH_CHECK(best_reward.numel() >= 1, "best_reward must not be empty");
+  // [0:2] iteration counters, [2:12] the per-phase cycle accumulators.
+  TORCH_CHECK(iter_counter.numel() >= 12,
+              "iter_counter must have >= 12 slots, got ",
+              iter_counter.numel());
+  TORCH_CHECK(inv_ls.numel() == dc, "inv_ls must have ", dc,
+              " elements, got ", inv_ls.numel());
+  TORCH_CHECK(alpha.numel() == n, "alpha must have ", n, " elements, got ",
+              alpha.numel());
+  TORCH_CHECK(kinv.dim() == 2 && kinv.size(0) == n && kinv.size(1) == n,
+              "kinv must be (", n, ", ", n, ")");
+  TORCH_CHECK(out_cont.numel() >= batch_size * dc,
+              "out_cont must hold batch * Dc elements");
+  TORCH_CHECK(k_ws.numel() >= batch_size * n,
+              "k_ws must hold batch * N elements");
+  TORCH_CHECK(mu_ws.numel() >= batch_size && dist_ws.numel() >= batch_size,
+              "mu_ws / dist_ws must hold batch elements");
   const long tiles_n = (n + 63) / 64;
   TORCH_CHECK(var_ws.numel() >= batch_size * (tiles_n * tiles_n + 1),
               "var_ws must be (B, tiles^2 + 1)");

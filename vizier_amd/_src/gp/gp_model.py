@@ -297,7 +297,12 @@ def nll_value_and_grad(raw: torch.Tensor, x: torch.Tensor,
 
   with the per-lengthscale traces reduced to GEMV forms
   (sum_ij A_ij (z_id - z_jd)^2 = 2 z_d^2 . rowsum(A) - 2 z_d^T A z_d
-  for symmetric A). Verified against autograd in tests/test_gp_core.py.
+  for symmetric A). Verified against fp64 autograd in
+  tests/test_gp_core.py and tests/test_fit_cases.py (CPU, the `k0`
+  branch); the fused GPU fp32 branch (K and G from one kernel, the
+  `k0 is None` amplitude trace, the HIP factorization and solve, the
+  ladder hints) is verified against the same fp64 oracle in
+  tests/test_fit_kernels.py.
 
   raw (R, D+3) -> (nll (R,), grad (R, D+3)).
   """
@@ -559,7 +564,8 @@ def train_gp(x: torch.Tensor, y: torch.Tensor, *,
   # trtri/trsm backward + serial rocblas trsv chain (warm refit
   # 146.8 -> 132.9 ms, headline bench 343 -> 324.7 ms; profiles/
   # fit_kernels_headline.txt). Gradients are the exact trace-identity
-  # values, verified against autograd in tests/test_gp_core.py.
+  # values, verified against fp64 autograd in tests/test_gp_core.py (CPU)
+  # and, for the fused GPU fp32 branch, in tests/test_fit_kernels.py.
   analytic_mode = os.environ.get('VIZIER_AMD_ANALYTIC_NLL', 'auto')
   use_analytic = (analytic_mode == 'always' or
                   (analytic_mode != 'never' and
@@ -574,7 +580,9 @@ def train_gp(x: torch.Tensor, y: torch.Tensor, *,
     # hipBLAS's trsm BACKWARD fails with ALLOC_FAILED at N~10^4 on
     # ROCm 7.2 (even unbatched), so huge studies cannot autograd the
     # NLL. Fit with ANALYTIC gradients instead (forward-only solves,
-    # verified against autograd to 1e-9 in tests/test_gp_core.py).
+    # verified against autograd to 1e-9 in fp64 on the CPU in
+    # tests/test_gp_core.py and tests/test_fit_cases.py; the GPU fp32
+    # branch to 4x the CPU fp32 error in tests/test_fit_kernels.py).
     # Ladder-cache: the line search returns its (L, info, z) per trial
     # so the gradient eval at the accepted point (bit-identical raw)
     # skips one full batched potrf, and on the HIP solve also the

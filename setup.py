@@ -25,7 +25,6 @@ _SRC = [
     'vizier_amd/_src/ops/csrc/eagle_sweep.hip',
     'vizier_amd/_src/ops/csrc/posterior_score_f64.hip',
     'vizier_amd/_src/ops/csrc/gram_matern52_f64.hip',
-    'vizier_amd/_src/ops/csrc/eagle_step_f64.hip',
 ]
 
 setup(

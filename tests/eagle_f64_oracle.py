@@ -1,4 +1,4 @@
-"""NumPy oracle of the Eagle step kernels (eagle_step.hip, eagle_step_f64.hip).
+"""NumPy oracle of the Eagle step kernels (eagle_step.hip, float and double).
 
 splitmix64 on np.uint64 with the constants of csrc/common.h, the 24-bit
 uniform, Laplace and Gumbel, and the suggest / update formulas of

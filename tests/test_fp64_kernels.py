@@ -3,7 +3,7 @@
   posterior_score_f64.hip  ps_kvec_f64 + ps_quadform_f64 (MFMA f64 16x16x4,
                            slabs, candidate tiles) + ps_finalize_f64
   gram_matern52_f64.hip    difference-form Gram / cross-Gram
-  eagle_step_f64.hip       suggest / update against tests/eagle_f64_oracle.py,
+  eagle_step.hip (double)  suggest / update against tests/eagle_f64_oracle.py,
                            at q = 1 and at q > 1
 
 Scorer operands are the fp32-valued cases of tests/scorer_cases.py, so

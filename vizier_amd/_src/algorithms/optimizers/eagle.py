@@ -73,7 +73,7 @@ class EagleState:
   best_reward: torch.Tensor      # scalar
 
 
-# Limits of the fused HIP step kernels (eagle_step.hip, eagle_step_f64.hip).
+# Limits of the fused HIP step kernels (eagle_step.hip, float and double).
 HIP_MAX_POOL = 128
 HIP_MAX_PARALLEL = 16
 
@@ -128,7 +128,7 @@ class VectorizedEagleStrategy:
     # The fused HIP path replaces the ~30-launch torch step with 2 launches.
     # fp64 sweeps (--fp64 parity mode) run the torch path on rocBLAS
     # DGEMMs unless VIZIER_AMD_FP64_HIP=1 selects the fp64 kernels
-    # (eagle_step_f64.hip; opt-in because their RNG stream differs from
+    # (eagle_step.hip in double; opt-in because their RNG stream differs from
     # the torch one). The flag is read here, at construction.
     from vizier_amd._src.ops import dispatch as ops
     self._f64_hip = (self.device.type == 'cuda' and

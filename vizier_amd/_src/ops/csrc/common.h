@@ -5,11 +5,69 @@
 
 #define WAVE_SIZE 64
 
+// Per-precision math for code templated over float / double. float keeps
+// the fast intrinsics the fp32 kernels have always used (exp -> __expf,
+// log -> __logf); double gets the accurate libm routines.
+template <typename T>
+struct vz_math;
+
+template <>
+struct vz_math<float> {
+  static __device__ __forceinline__ float fma(float a, float b, float c) {
+    return fmaf(a, b, c);
+  }
+  static __device__ __forceinline__ float fmax(float a, float b) {
+    return fmaxf(a, b);
+  }
+  static __device__ __forceinline__ float fmin(float a, float b) {
+    return fminf(a, b);
+  }
+  static __device__ __forceinline__ float fabs(float a) { return fabsf(a); }
+  static __device__ __forceinline__ float exp(float a) { return __expf(a); }
+  static __device__ __forceinline__ float log(float a) { return __logf(a); }
+  static __device__ __forceinline__ float log1p(float a) {
+    return log1pf(a);
+  }
+  static __device__ __forceinline__ float sqrt(float a) { return sqrtf(a); }
+};
+
+template <>
+struct vz_math<double> {
+  static __device__ __forceinline__ double fma(double a, double b,
+                                               double c) {
+    return ::fma(a, b, c);
+  }
+  static __device__ __forceinline__ double fmax(double a, double b) {
+    return ::fmax(a, b);
+  }
+  static __device__ __forceinline__ double fmin(double a, double b) {
+    return ::fmin(a, b);
+  }
+  static __device__ __forceinline__ double fabs(double a) {
+    return ::fabs(a);
+  }
+  static __device__ __forceinline__ double exp(double a) { return ::exp(a); }
+  static __device__ __forceinline__ double log(double a) { return ::log(a); }
+  static __device__ __forceinline__ double log1p(double a) {
+    return ::log1p(a);
+  }
+  static __device__ __forceinline__ double sqrt(double a) {
+    return ::sqrt(a);
+  }
+};
+
+// k(r) = (1 + sqrt5*r + 5r^2/3) exp(-sqrt5*r), r = sqrt(d2). The two
+// precisions are separate formulas on purpose: fp32 multiplies by 1/3 and
+// uses the fast exp, fp64 divides by 3 and uses the correctly-rounded /
+// <1 ulp double sqrt and exp.
 __device__ __forceinline__ float matern52_of_d2(float d2) {
-  // k(r) = (1 + sqrt5*r + 5r^2/3) exp(-sqrt5*r), r = sqrt(d2)
   const float r = sqrtf(fmaxf(d2, 0.0f));
   const float sr = 2.2360679774997896f * r;  // sqrt(5) * r
   return (1.0f + sr + sr * sr * (1.0f / 3.0f)) * __expf(-sr);
+}
+__device__ __forceinline__ double matern52_of_d2(double d2) {
+  const double sr = 2.23606797749978969641 * sqrt(fmax(d2, 0.0));
+  return (1.0 + sr + sr * sr / 3.0) * exp(-sr);
 }
 
 // Eight OCP e4m3 bytes (byte 0 = element 0) -> eight bf16, exactly: e4m3's
@@ -66,10 +124,11 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
-// Block-level reduction: 256 threads = 4 waves -> LDS -> wave 0.
-template <typename Op>
-__device__ __forceinline__ float block_reduce(float v, float* lds4,
-                                              Op op, float init) {
+// Block-level reduction: up to 4 waves -> LDS -> wave 0. The shuffle tree
+// and the LDS pass have a fixed shape, so the result is run-to-run
+// deterministic.
+template <typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, T* lds4, Op op, T init) {
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
 #pragma unroll
@@ -99,23 +158,27 @@ __device__ __forceinline__ unsigned long long vz_splitmix64(
   return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ float vz_rng_uniform(unsigned long long seed,
-                                                unsigned long long offset,
-                                                unsigned int idx) {
-  // 24 bits k -> (k + 0.5) 2^-24 in (0, 1]. The sum is a float: exact
-  // for k < 2^23, rounded to even above (two k share a value), and
+template <typename T>
+__device__ __forceinline__ T vz_rng_uniform(unsigned long long seed,
+                                            unsigned long long offset,
+                                            unsigned int idx) {
+  // 24 bits k -> (k + 0.5) 2^-24 in (0, 1]. Both precisions draw the same
+  // k. In double the sum is exact (25 significant bits). In float it is
+  // exact for k < 2^23, rounded to even above (two k share a value), and
   // k = 2^24 - 1 gives exactly 1.0f. Callers tolerate the endpoint: the
   // Laplace draw clamps |u - 0.5|, the refill takes min(c, size - 1).
   unsigned long long h = vz_splitmix64(seed ^ vz_splitmix64(offset ^ idx));
-  return ((h >> 40) + 0.5f) * (1.0f / 16777216.0f);
+  return (T(h >> 40) + T(0.5)) * (T(1) / T(16777216));
 }
 
-__device__ __forceinline__ float vz_rng_laplace(unsigned long long seed,
-                                                unsigned long long offset,
-                                                unsigned int idx) {
-  const float u = vz_rng_uniform(seed, offset, idx) - 0.5f;
-  const float a = fminf(fabsf(u), 0.499999f);
-  return (u >= 0.0f ? -1.0f : 1.0f) * log1pf(-2.0f * a);
+template <typename T>
+__device__ __forceinline__ T vz_rng_laplace(unsigned long long seed,
+                                            unsigned long long offset,
+                                            unsigned int idx) {
+  using M = vz_math<T>;
+  const T u = vz_rng_uniform<T>(seed, offset, idx) - T(0.5);
+  const T a = M::fmin(M::fabs(u), T(0.499999));
+  return (u >= T(0) ? T(-1) : T(1)) * M::log1p(T(-2) * a);
 }
 
 __device__ __forceinline__ float vz_normal_cdf(float z) {
@@ -123,6 +186,48 @@ __device__ __forceinline__ float vz_normal_cdf(float z) {
 }
 __device__ __forceinline__ float vz_normal_pdf(float z) {
   return 0.3989422804014327f * __expf(-0.5f * z * z);
+}
+__device__ __forceinline__ double vz_normal_cdf(double z) {
+  return 0.5 * erfc(-z * 0.70710678118654752440);
+}
+__device__ __forceinline__ double vz_normal_pdf(double z) {
+  return 0.39894228040143267794 * exp(-0.5 * z * z);
+}
+
+// Acquisition codes of every scorer (ops/dispatch.py passes them through).
+#define ACQ_UCB 0
+#define ACQ_LCB 1
+#define ACQ_EI 2
+#define ACQ_PI 3
+#define ACQ_MEAN 4
+#define ACQ_STDDEV 5
+
+template <typename T>
+__device__ __forceinline__ T vz_acq_score(int acq, T mu, T sd, T coef,
+                                          T best_value) {
+  switch (acq) {
+    case ACQ_LCB: return mu - coef * sd;
+    case ACQ_EI: {
+      const T z = (mu - best_value) / sd;
+      return sd * (z * vz_normal_cdf(z) + vz_normal_pdf(z));
+    }
+    case ACQ_PI: return vz_normal_cdf((mu - best_value) / sd);
+    case ACQ_MEAN: return mu;
+    case ACQ_STDDEV: return sd;
+    case ACQ_UCB:
+    default: return mu + coef * sd;
+  }
+}
+
+// Trust region: a candidate farther than tr_radius (min L-inf distance to
+// the training points) scores -1e4 - dist. A radius outside (0, 0.5]
+// switches the region off.
+template <typename T>
+__device__ __forceinline__ T vz_trust_region(T score, T dist, T tr_radius) {
+  if (tr_radius > T(0) && tr_radius <= T(0.5) && dist > tr_radius) {
+    return T(-1e4) - dist;
+  }
+  return score;
 }
 
 // ---- Shared 64x64-tile K^-1 quadform --------------------------------------

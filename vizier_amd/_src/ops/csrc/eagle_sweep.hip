@@ -52,13 +52,6 @@
 #define SWEEP_NCHUNK 10   // must match posterior_score.hip's NCHUNK
 #define POOL_LDS_CAP 8192  // floats: stage pool in LDS when it fits
 
-#define ACQ_UCB 0
-#define ACQ_LCB 1
-#define ACQ_EI 2
-#define ACQ_PI 3
-#define ACQ_MEAN 4
-#define ACQ_STDDEV 5
-
 // Agent-scope (device) coherent access helpers: compile to memory-side
 // accesses that bypass the incoherent per-XCD L2 path for plain loads.
 __device__ __forceinline__ float cload(const float* p) {
@@ -109,22 +102,6 @@ __device__ __forceinline__ void grid_sync(unsigned int* bar) {
     asm volatile("" ::: "memory");
   }
   __syncthreads();
-}
-
-__device__ __forceinline__ float acq_score(int acq, float mu, float sd,
-                                           float coef, float best_value) {
-  switch (acq) {
-    case ACQ_LCB: return mu - coef * sd;
-    case ACQ_EI: {
-      const float z = (mu - best_value) / sd;
-      return sd * (z * vz_normal_cdf(z) + vz_normal_pdf(z));
-    }
-    case ACQ_PI: return vz_normal_cdf((mu - best_value) / sd);
-    case ACQ_MEAN: return mu;
-    case ACQ_STDDEV: return sd;
-    case ACQ_UCB:
-    default: return mu + coef * sd;
-  }
 }
 
 extern "C" __global__ __launch_bounds__(BLOCK) void
@@ -259,7 +236,7 @@ eagle_sweep_kernel(
         const float mine = stage_pool ? pool_lds[me * dc + j]
                                       : cload(pool_cont + me * dc + j);
         moved = mine + (moved - mine * scale_sum);
-        float noise = vz_rng_laplace(seed_suggest, offset,
+        float noise = vz_rng_laplace<float>(seed_suggest, offset,
                                      (unsigned)(b * dc + j));
         noise = (noise >= 0.0f) ? 1.0f : -1.0f;  // q == 1
         const float cand = moved + noise * my_pert;
@@ -358,11 +335,9 @@ eagle_sweep_kernel(
         float var = fmaxf(amp2 - quad, 1e-12f);
         const float sd = sqrtf(var);
         const float mu = cload(mu_ws + t) + mean_c;
-        float score = acq_score(acq, mu, sd, coef, best_value);
-        const float dist = cload(dist_ws + t);
-        if (tr_radius > 0.0f && tr_radius <= 0.5f && dist > tr_radius) {
-          score = -1e4f - dist;
-        }
+        const float score = vz_trust_region(
+            vz_acq_score(acq, mu, sd, coef, best_value),
+            cload(dist_ws + t), tr_radius);
         local_max = fmaxf(local_max, score);
         if (t == i) my_score = score;
       }
@@ -394,7 +369,7 @@ eagle_sweep_kernel(
       if (dead) {
         for (int j = tid; j < dc; j += BLOCK) {
           cstore(pool_cont + me * dc + j,
-                 vz_rng_uniform(seed_update, offset ^ 0x5151ull,
+                 vz_rng_uniform<float>(seed_update, offset ^ 0x5151ull,
                                 (unsigned)(me * dc + j)));
         }
         reward = -INFINITY;

@@ -9,7 +9,7 @@
 // Numeric spec: vizier_amd/_src/gp/matern.py::gram_matern52 in float64.
 
 #include <hip/hip_runtime.h>
-#include "common_f64.h"
+#include "common.h"
 
 #define TILE 16
 #define DCHUNK 32
@@ -55,7 +55,7 @@ gram_matern52_f64_kernel(const double* __restrict__ x1,
   const int row = row0 + ty;
   const int col = col0 + tx;
   if (row < n && col < m) {
-    const double k = amp2 * vz_matern52_of_d2_f64(acc);
+    const double k = amp2 * matern52_of_d2(acc);
     out[(long)row * m + col] = k;
     // Mirror the strictly-upper tiles; in the diagonal tile both (r, c)
     // and (c, r) are computed (bitwise equal: the difference only flips

@@ -178,7 +178,7 @@ extern "C" void launch_eagle_update(
     hipStream_t stream);
 
 // fp64 parity-mode kernels (posterior_score_f64.hip, gram_matern52_f64.hip,
-// eagle_step_f64.hip).
+// the double instantiations of eagle_step.hip).
 extern "C" void ps_f64_quadform_shape(int n, int* ctiles, int* slabs,
                                       int* slab_rows);
 
@@ -533,6 +533,121 @@ torch::Tensor quadform_large_n(const torch::Tensor& k_ws,
   return (k_ws * t).sum(-1);
 }
 
+// -- Pieces of the fused scorer pipeline ---------------------------------
+//
+// posterior_scores_chunked, posterior_scores_bf16, posterior_mean_std and
+// posterior_mean_std_fp8 all run: k-vector kernel -> quadform by one of
+// three routes -> finalize.
+
+// Large-N quadform via one rocBLAS SGEMM: K_inv is read ONCE per
+// iteration instead of once per candidate (the per-candidate streaming
+// path moves b * N^2 * 4 bytes of HBM per call — 10 GB at N=10^4, B=25 —
+// and measured 4.2 ms/iter on BASELINE config 4). Crossover default 4096
+// (below that K_inv is L2/MALL-resident and the fused kernels win on
+// launch count); override with VIZIER_AMD_PS_GEMM_N.
+int gemm_n_threshold() {
+  static const int threshold = []() {
+    const char* s = getenv("VIZIER_AMD_PS_GEMM_N");
+    return s ? atoi(s) : 4096;
+  }();
+  return threshold;
+}
+
+enum class QuadRoute { kGemm, kTile, kLegacy };
+
+QuadRoute quad_route(int n, int b) {
+  if (n >= gemm_n_threshold()) return QuadRoute::kGemm;
+  return b <= 32 ? QuadRoute::kTile : QuadRoute::kLegacy;
+}
+
+// What every k-vector kernel writes: k (b, n), mu (b,) without the mean
+// constant, dist (b,) min L-inf distance to the training points.
+struct ScorerWs {
+  torch::Tensor k, mu, dist;
+  ScorerWs(const torch::Tensor& xq, int n)
+      : k(torch::empty({xq.size(0), n}, xq.options())),
+        mu(torch::empty({xq.size(0)}, xq.options())),
+        dist(torch::empty({xq.size(0)}, xq.options())) {}
+};
+
+struct AcqArgs {
+  float amp2, mean_c;
+  int acq;
+  float coef, best_value, tr_radius;
+};
+
+// The fp32 k-vector: one workgroup per candidate, or the row-split
+// variant that fills the chip at large N.
+void kvec_f32(const torch::Tensor& xq, const torch::Tensor& x,
+              const torch::Tensor& inv_ls, const torch::Tensor& alpha,
+              const torch::Tensor& onehot, ScorerWs& ws, float amp2,
+              bool split) {
+  const int b = xq.size(0), d = xq.size(1), n = x.size(0);
+  if (!split) {
+    launch_ps_kvec(
+        xq.data_ptr<float>(), x.data_ptr<float>(),
+        inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
+        onehot.data_ptr<unsigned char>(), ws.k.data_ptr<float>(),
+        ws.mu.data_ptr<float>(), ws.dist.data_ptr<float>(), b, n, d, amp2,
+        current_stream());
+    return;
+  }
+  const int rchunks = std::max(1, 512 / std::max(b, 1));
+  auto mu_part = torch::empty({b, rchunks}, xq.options());
+  auto dist_part = torch::empty({b, rchunks}, xq.options());
+  launch_ps_kvec_split(
+      xq.data_ptr<float>(), x.data_ptr<float>(), inv_ls.data_ptr<float>(),
+      alpha.data_ptr<float>(), onehot.data_ptr<unsigned char>(),
+      ws.k.data_ptr<float>(), mu_part.data_ptr<float>(),
+      dist_part.data_ptr<float>(), ws.mu.data_ptr<float>(),
+      ws.dist.data_ptr<float>(), b, n, d, amp2, rchunks, current_stream());
+}
+
+// The (b,) quadform by the GEMM or the tile route. The legacy NCHUNK
+// route has no common form: each binding has its own launcher for it.
+torch::Tensor quadform(QuadRoute route, const ScorerWs& ws,
+                       const torch::Tensor& kinv) {
+  const int b = ws.k.size(0), n = ws.k.size(1);
+  return route == QuadRoute::kTile
+      ? quadform_tile_small_n(ws.k, kinv, b, n, current_stream())
+      : quadform_large_n(ws.k, kinv, b, n, current_stream());
+}
+
+torch::Tensor finalize_score(const ScorerWs& ws, const torch::Tensor& quad,
+                             const AcqArgs& a) {
+  const int b = ws.mu.size(0);
+  auto out = torch::empty({b}, ws.mu.options());
+  launch_ps_finalize_direct(
+      ws.mu.data_ptr<float>(), ws.dist.data_ptr<float>(),
+      quad.data_ptr<float>(), out.data_ptr<float>(), b, a.amp2, a.mean_c,
+      a.acq, a.coef, a.best_value, a.tr_radius, current_stream());
+  return out;
+}
+
+// var is the (b,) quadform (nchunk == 0) or (b, nchunk) partial sums.
+std::vector<torch::Tensor> finalize_meanstd(const ScorerWs& ws,
+                                            const torch::Tensor& var,
+                                            int nchunk, float amp2,
+                                            float mean_c) {
+  const int b = ws.mu.size(0);
+  auto mean = torch::empty({b}, ws.mu.options());
+  auto sd = torch::empty({b}, ws.mu.options());
+  if (nchunk == 0) {
+    launch_ps_finalize_meanstd_direct(
+        ws.mu.data_ptr<float>(), var.data_ptr<float>(),
+        mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2, mean_c,
+        current_stream());
+  } else {
+    launch_ps_finalize_meanstd(
+        ws.mu.data_ptr<float>(), var.data_ptr<float>(),
+        mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2, mean_c,
+        nchunk, current_stream());
+  }
+  return {mean, sd, ws.dist};
+}
+
+constexpr int kLegacyNchunk = 10;  // NCHUNK of posterior_score.hip
+
 }  // namespace
 
 torch::Tensor gram_matern52_fp8_pre(
@@ -592,69 +707,31 @@ torch::Tensor posterior_scores_chunked(
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   TORCH_CHECK(d <= 512, "posterior_scores supports D <= 512");
   auto inv_ls = 1.0f / lengthscales;
-  auto k_ws = torch::empty({b, n}, xq.options());
-  auto mu_ws = torch::empty({b}, xq.options());
-  auto dist_ws = torch::empty({b}, xq.options());
-  auto out = torch::empty({b}, xq.options());
-  // Large-N quadform via one rocBLAS SGEMM: K_inv is read ONCE per
-  // iteration instead of once per candidate (the per-candidate
-  // streaming path moves b * N^2 * 4 bytes of HBM per call — 10 GB at
-  // N=10^4, B=25 — and measured 4.2 ms/iter on BASELINE config 4).
-  // Crossover default 4096 (below that K_inv is L2/MALL-resident and
-  // the fused kernel wins on launch count); override with
-  // VIZIER_AMD_PS_GEMM_N.
-  static const int gemm_n_threshold = []() {
-    const char* s = getenv("VIZIER_AMD_PS_GEMM_N");
-    return s ? atoi(s) : 4096;
-  }();
-  if (n >= gemm_n_threshold) {
-    const int rchunks = std::max(1, 512 / std::max(b, 1));
-    auto mu_part = torch::empty({b, rchunks}, xq.options());
-    auto dist_part = torch::empty({b, rchunks}, xq.options());
-    launch_ps_kvec_split(
-        xq.data_ptr<float>(), x.data_ptr<float>(),
-        inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
-        onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-        mu_part.data_ptr<float>(), dist_part.data_ptr<float>(),
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(), b, n, d,
-        (float)(amplitude * amplitude), rchunks, current_stream());
-    auto quad = quadform_large_n(k_ws, kinv, b, n, current_stream());
-    launch_ps_finalize_direct(
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-        quad.data_ptr<float>(), out.data_ptr<float>(), b,
-        (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-        (float)coef, (float)best_value, (float)tr_radius,
+  const AcqArgs a{(float)(amplitude * amplitude), (float)mean_c, (int)acq,
+                  (float)coef, (float)best_value, (float)tr_radius};
+  const QuadRoute route = quad_route(n, b);
+  ScorerWs ws(xq, n);
+  if (route == QuadRoute::kLegacy) {
+    // This binding's legacy path is one launcher for all three kernels:
+    // ps_kvec, the NCHUNK quadform, ps_finalize.
+    auto var_ws = torch::empty({b, kLegacyNchunk}, xq.options());
+    auto out = torch::empty({b}, xq.options());
+    launch_posterior_score_chunked(
+        xq.data_ptr<float>(), x.data_ptr<float>(), inv_ls.data_ptr<float>(),
+        alpha.data_ptr<float>(), kinv.data_ptr<float>(),
+        onehot.data_ptr<unsigned char>(), ws.k.data_ptr<float>(),
+        ws.mu.data_ptr<float>(), ws.dist.data_ptr<float>(),
+        var_ws.data_ptr<float>(), out.data_ptr<float>(), b, n, d, a.amp2,
+        a.mean_c, a.acq, a.coef, a.best_value, a.tr_radius,
         current_stream());
     return out;
   }
-  if (b <= 32) {
-    launch_ps_kvec(
-        xq.data_ptr<float>(), x.data_ptr<float>(),
-        inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
-        onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(), b, n, d,
-        (float)(amplitude * amplitude), current_stream());
-    auto quad = quadform_tile_small_n(k_ws, kinv, b, n,
-                                      current_stream());
-    launch_ps_finalize_direct(
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-        quad.data_ptr<float>(), out.data_ptr<float>(), b,
-        (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-        (float)coef, (float)best_value, (float)tr_radius,
-        current_stream());
-    return out;
-  }
-  auto var_ws = torch::empty({b, 10}, xq.options());
-  launch_posterior_score_chunked(
-      xq.data_ptr<float>(), x.data_ptr<float>(), inv_ls.data_ptr<float>(),
-      alpha.data_ptr<float>(), kinv.data_ptr<float>(),
-      onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-      mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-      var_ws.data_ptr<float>(), out.data_ptr<float>(), b, n, d,
-      (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-      (float)coef, (float)best_value, (float)tr_radius,
-      current_stream());
-  return out;
+  // The fp32 bindings (this one and posterior_mean_std) switch to the
+  // row-split k-vector on the GEMM route; bf16 and fp8 have one k-vector
+  // kernel each for every N.
+  kvec_f32(xq, x, inv_ls, alpha, onehot, ws, a.amp2,
+           route == QuadRoute::kGemm);
+  return finalize_score(ws, quadform(route, ws, kinv), a);
 }
 
 // -- Monte-Carlo qEI over candidate sets (qei_score.hip) ------------------
@@ -807,51 +884,31 @@ torch::Tensor posterior_scores_bf16(
   TORCH_CHECK(dp % 32 == 0 && dp <= 512, "dp must be mult of 32, <=512");
   TORCH_CHECK(dp >= d, "z2b must have at least ", d, " columns");
   auto inv_ls = 1.0f / lengthscales;
-  auto k_ws = torch::empty({b, n}, xq.options());
-  auto mu_ws = torch::empty({b}, xq.options());
-  auto dist_ws = torch::empty({b}, xq.options());
-  auto out = torch::empty({b}, xq.options());
+  const AcqArgs a{(float)(amplitude * amplitude), (float)mean_c, (int)acq,
+                  (float)coef, (float)best_value, (float)tr_radius};
+  ScorerWs ws(xq, n);
   launch_ps_kvec_bf16(
       xq.data_ptr<float>(), x.data_ptr<float>(),
       (const unsigned short*)z2b.data_ptr(), n2.data_ptr<float>(),
       inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
-      onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-      mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(), b, n, d, dp,
-      (float)(amplitude * amplitude), current_stream());
-  static const int gemm_n_threshold = []() {
-    const char* s = getenv("VIZIER_AMD_PS_GEMM_N");
-    return s ? atoi(s) : 4096;
-  }();
-  if (n >= gemm_n_threshold) {
-    auto quad = quadform_large_n(k_ws, kinv, b, n, current_stream());
-    launch_ps_finalize_direct(
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-        quad.data_ptr<float>(), out.data_ptr<float>(), b,
-        (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-        (float)coef, (float)best_value, (float)tr_radius,
+      onehot.data_ptr<unsigned char>(), ws.k.data_ptr<float>(),
+      ws.mu.data_ptr<float>(), ws.dist.data_ptr<float>(), b, n, d, dp,
+      a.amp2, current_stream());
+  const QuadRoute route = quad_route(n, b);
+  if (route == QuadRoute::kLegacy) {
+    // This binding's legacy path: one launcher for the NCHUNK quadform
+    // and ps_finalize.
+    auto var_ws = torch::empty({b, kLegacyNchunk}, xq.options());
+    auto out = torch::empty({b}, xq.options());
+    launch_ps_quadform_finalize(
+        ws.k.data_ptr<float>(), kinv.data_ptr<float>(),
+        ws.mu.data_ptr<float>(), ws.dist.data_ptr<float>(),
+        var_ws.data_ptr<float>(), out.data_ptr<float>(), b, n, a.amp2,
+        a.mean_c, a.acq, a.coef, a.best_value, a.tr_radius,
         current_stream());
     return out;
   }
-  if (b <= 32) {
-    auto quad = quadform_tile_small_n(k_ws, kinv, b, n,
-                                      current_stream());
-    launch_ps_finalize_direct(
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-        quad.data_ptr<float>(), out.data_ptr<float>(), b,
-        (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-        (float)coef, (float)best_value, (float)tr_radius,
-        current_stream());
-    return out;
-  }
-  auto var_ws = torch::empty({b, 10}, xq.options());
-  launch_ps_quadform_finalize(
-      k_ws.data_ptr<float>(), kinv.data_ptr<float>(),
-      mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-      var_ws.data_ptr<float>(), out.data_ptr<float>(), b, n,
-      (float)(amplitude * amplitude), (float)mean_c, (int)acq,
-      (float)coef, (float)best_value, (float)tr_radius,
-      current_stream());
-  return out;
+  return finalize_score(ws, quadform(route, ws, kinv), a);
 }
 
 std::vector<torch::Tensor> posterior_mean_std(
@@ -870,58 +927,23 @@ std::vector<torch::Tensor> posterior_mean_std(
   const int b = xq.size(0), d = xq.size(1), n = x.size(0);
   TORCH_CHECK(d <= 512, "posterior_mean_std supports D <= 512");
   auto inv_ls = 1.0f / lengthscales;
-  auto k_ws = torch::empty({b, n}, xq.options());
-  auto mu_ws = torch::empty({b}, xq.options());
-  auto dist_ws = torch::empty({b}, xq.options());
-  auto mean = torch::empty({b}, xq.options());
-  auto sd = torch::empty({b}, xq.options());
   const float amp2 = (float)(amplitude * amplitude);
-  static const int gemm_n_threshold = []() {
-    const char* s = getenv("VIZIER_AMD_PS_GEMM_N");
-    return s ? atoi(s) : 4096;
-  }();
-  if (n >= gemm_n_threshold) {
-    const int rchunks = std::max(1, 512 / std::max(b, 1));
-    auto mu_part = torch::empty({b, rchunks}, xq.options());
-    auto dist_part = torch::empty({b, rchunks}, xq.options());
-    launch_ps_kvec_split(
-        xq.data_ptr<float>(), x.data_ptr<float>(),
-        inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
-        onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-        mu_part.data_ptr<float>(), dist_part.data_ptr<float>(),
-        mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(), b, n, d,
-        amp2, rchunks, current_stream());
-    auto quad = quadform_large_n(k_ws, kinv, b, n, current_stream());
-    launch_ps_finalize_meanstd_direct(
-        mu_ws.data_ptr<float>(), quad.data_ptr<float>(),
-        mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2,
-        (float)mean_c, current_stream());
-    return {mean, sd, dist_ws};
+  const QuadRoute route = quad_route(n, b);
+  ScorerWs ws(xq, n);
+  kvec_f32(xq, x, inv_ls, alpha, onehot, ws, amp2,
+           route == QuadRoute::kGemm);
+  if (route == QuadRoute::kLegacy) {
+    // This binding's legacy path: the NCHUNK quadform alone, then the
+    // partial-sum form of the finalize.
+    auto var_ws = torch::empty({b, kLegacyNchunk}, xq.options());
+    launch_ps_quadform_kernel_only(
+        ws.k.data_ptr<float>(), kinv.data_ptr<float>(),
+        var_ws.data_ptr<float>(), b, n, current_stream());
+    return finalize_meanstd(ws, var_ws, kLegacyNchunk, amp2,
+                            (float)mean_c);
   }
-  launch_ps_kvec(
-      xq.data_ptr<float>(), x.data_ptr<float>(),
-      inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
-      onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
-      mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(), b, n, d,
-      amp2, current_stream());
-  if (b <= 32) {
-    auto quad = quadform_tile_small_n(k_ws, kinv, b, n,
-                                      current_stream());
-    launch_ps_finalize_meanstd_direct(
-        mu_ws.data_ptr<float>(), quad.data_ptr<float>(),
-        mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2,
-        (float)mean_c, current_stream());
-    return {mean, sd, dist_ws};
-  }
-  auto var_ws = torch::empty({b, 10}, xq.options());
-  launch_ps_quadform_kernel_only(
-      k_ws.data_ptr<float>(), kinv.data_ptr<float>(),
-      var_ws.data_ptr<float>(), b, n, current_stream());
-  launch_ps_finalize_meanstd(
-      mu_ws.data_ptr<float>(), var_ws.data_ptr<float>(),
-      mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2,
-      (float)mean_c, 10, current_stream());
-  return {mean, sd, dist_ws};
+  return finalize_meanstd(ws, quadform(route, ws, kinv), 0, amp2,
+                          (float)mean_c);
 }
 
 std::vector<torch::Tensor> posterior_mean_std_fp8(
@@ -957,32 +979,23 @@ std::vector<torch::Tensor> posterior_mean_std_fp8(
                  (z1 / scale).to(torch::kFloat8_e4m3fn));
   auto z1f = z1q.to(torch::kFloat32) * scale;
   auto n1 = (z1f * z1f).sum(-1);
-  auto k_ws = torch::empty({b, n}, xq.options());
-  auto mu_ws = torch::empty({b}, xq.options());
-  auto dist_ws = torch::empty({b}, xq.options());
-  auto mean = torch::empty({b}, xq.options());
-  auto sd = torch::empty({b}, xq.options());
   const float amp2 = (float)(amplitude * amplitude);
+  ScorerWs ws(xq, n);
   launch_ps_kvec_fp8(
       z1f.contiguous().data_ptr<float>(), n1.contiguous().data_ptr<float>(),
       xq.data_ptr<float>(), x.data_ptr<float>(),
       (const unsigned char*)z2q.data_ptr(), n2.data_ptr<float>(),
       alpha.data_ptr<float>(), onehot.data_ptr<unsigned char>(),
-      k_ws.data_ptr<float>(), mu_ws.data_ptr<float>(),
-      dist_ws.data_ptr<float>(), b, n, d, dp, amp2, (float)scale,
+      ws.k.data_ptr<float>(), ws.mu.data_ptr<float>(),
+      ws.dist.data_ptr<float>(), b, n, d, dp, amp2, (float)scale,
       current_stream());
-  static const int gemm_n_threshold = []() {
-    const char* sE = getenv("VIZIER_AMD_PS_GEMM_N");
-    return sE ? atoi(sE) : 4096;
-  }();
-  auto quad = (n < gemm_n_threshold && b <= 32)
-      ? quadform_tile_small_n(k_ws, kinv, b, n, current_stream())
-      : quadform_large_n(k_ws, kinv, b, n, current_stream());
-  launch_ps_finalize_meanstd_direct(
-      mu_ws.data_ptr<float>(), quad.data_ptr<float>(),
-      mean.data_ptr<float>(), sd.data_ptr<float>(), b, amp2,
-      (float)mean_c, current_stream());
-  return {mean, sd, dist_ws};
+  // This binding has no legacy NCHUNK path: below the threshold, b > 32
+  // goes to the GEMM route where the other three take their legacy
+  // kernels.
+  const QuadRoute route = quad_route(n, b) == QuadRoute::kTile
+      ? QuadRoute::kTile : QuadRoute::kGemm;
+  return finalize_meanstd(ws, quadform(route, ws, kinv), 0, amp2,
+                          (float)mean_c);
 }
 
 // -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
@@ -1220,10 +1233,9 @@ torch::Tensor batched_trsv_lower(torch::Tensor L, torch::Tensor b,
 
 // -- Eagle step bindings ------------------------------------------------------
 //
-// The fp32 (eagle_step.hip) and fp64 (eagle_step_f64.hip) kernels have
-// the same shape limits and index the same way, so the two pairs of
-// bindings share their argument checks. Every check throws before
-// anything is launched.
+// The fp32 and fp64 kernels are instantiations of one template
+// (eagle_step.hip), so the two pairs of bindings share their argument
+// checks and their bodies. Every check throws before anything is launched.
 
 torch::Tensor check_f64(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
@@ -1356,7 +1368,11 @@ EagleShape check_eagle_update_args(
   return s;
 }
 
-std::vector<torch::Tensor> eagle_suggest(
+// One body per step for both precisions. Launch is the extern "C" launcher
+// of the kernel's instantiation for T; the double arguments are narrowed
+// to T here.
+template <typename T, auto Launch>
+std::vector<torch::Tensor> eagle_suggest_impl(
     torch::Tensor pool_cont, torch::Tensor pool_cat, torch::Tensor rewards,
     torch::Tensor perturbations, torch::Tensor cat_sizes,
     torch::Tensor iter_counter, int64_t n_batches, int64_t batch_size,
@@ -1365,50 +1381,58 @@ std::vector<torch::Tensor> eagle_suggest(
     torch::Tensor out_cont, torch::Tensor out_cat, int64_t max_cat) {
   const EagleShape s = check_eagle_suggest_args(
       pool_cont, pool_cat, rewards, perturbations, cat_sizes, iter_counter,
-      n_batches, batch_size, out_cont, out_cat, max_cat, torch::kFloat32);
-  launch_eagle_suggest(
-      pool_cont.data_ptr<float>(),
+      n_batches, batch_size, out_cont, out_cat, max_cat,
+      c10::CppTypeToScalarType<T>::value);
+  Launch(
+      pool_cont.data_ptr<T>(),
       s.dcat ? pool_cat.data_ptr<long>() : nullptr,
-      rewards.data_ptr<float>(), perturbations.data_ptr<float>(),
+      rewards.data_ptr<T>(), perturbations.data_ptr<T>(),
       s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
-      out_cont.data_ptr<float>(),
+      out_cont.data_ptr<T>(),
       s.dcat ? out_cat.data_ptr<long>() : nullptr,
       (const unsigned long long*)iter_counter.data_ptr<int64_t>(),
       (int)n_batches, s.batch_size, s.pool_size, s.q, s.dc, s.dcat,
-      (int)max_cat, (float)visibility,
-      (float)gravity, (float)neg_gravity, (float)norm_scale,
-      (float)cat_factor, (float)p_same, (unsigned long long)seed,
+      (int)max_cat, (T)visibility, (T)gravity, (T)neg_gravity,
+      (T)norm_scale, (T)cat_factor, (T)p_same, (unsigned long long)seed,
       current_stream());
   return {out_cont, out_cat};
 }
 
-void eagle_update(torch::Tensor pool_cont, torch::Tensor pool_cat,
-                  torch::Tensor rewards, torch::Tensor perturbations,
-                  torch::Tensor batch_cont, torch::Tensor batch_cat,
-                  torch::Tensor batch_rewards, torch::Tensor cat_sizes,
-                  torch::Tensor best_reward, torch::Tensor iter_counter,
-                  int64_t n_batches,
-                  double penalize_factor, double perturbation_lower_bound,
-                  double base_perturbation, int64_t seed) {
+template <typename T, auto Launch>
+void eagle_update_impl(
+    torch::Tensor pool_cont, torch::Tensor pool_cat, torch::Tensor rewards,
+    torch::Tensor perturbations, torch::Tensor batch_cont,
+    torch::Tensor batch_cat, torch::Tensor batch_rewards,
+    torch::Tensor cat_sizes, torch::Tensor best_reward,
+    torch::Tensor iter_counter, int64_t n_batches, double penalize_factor,
+    double perturbation_lower_bound, double base_perturbation,
+    int64_t seed) {
   const EagleShape s = check_eagle_update_args(
       pool_cont, pool_cat, rewards, perturbations, batch_cont, batch_cat,
       batch_rewards, cat_sizes, best_reward, iter_counter, n_batches,
-      torch::kFloat32);
-  launch_eagle_update(
-      pool_cont.data_ptr<float>(),
+      c10::CppTypeToScalarType<T>::value);
+  Launch(
+      pool_cont.data_ptr<T>(),
       s.dcat ? pool_cat.data_ptr<long>() : nullptr,
-      rewards.data_ptr<float>(), perturbations.data_ptr<float>(),
-      batch_cont.data_ptr<float>(),
+      rewards.data_ptr<T>(), perturbations.data_ptr<T>(),
+      batch_cont.data_ptr<T>(),
       s.dcat ? batch_cat.data_ptr<long>() : nullptr,
-      batch_rewards.data_ptr<float>(),
+      batch_rewards.data_ptr<T>(),
       s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
-      best_reward.data_ptr<float>(),
+      best_reward.data_ptr<T>(),
       (unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, s.batch_size, s.q, s.dc,
-      s.dcat, (float)penalize_factor, (float)perturbation_lower_bound,
-      (float)base_perturbation, (unsigned long long)seed,
-      current_stream());
+      (int)n_batches, s.batch_size, s.q, s.dc, s.dcat, (T)penalize_factor,
+      (T)perturbation_lower_bound, (T)base_perturbation,
+      (unsigned long long)seed, current_stream());
 }
+
+constexpr auto eagle_suggest =
+    &eagle_suggest_impl<float, launch_eagle_suggest>;
+constexpr auto eagle_suggest_f64 =
+    &eagle_suggest_impl<double, launch_eagle_suggest_f64>;
+constexpr auto eagle_update = &eagle_update_impl<float, launch_eagle_update>;
+constexpr auto eagle_update_f64 =
+    &eagle_update_impl<double, launch_eagle_update_f64>;
 
 int64_t eagle_sweep(
     torch::Tensor pool_cont, torch::Tensor rewards,
@@ -1603,57 +1627,6 @@ torch::Tensor gram_matern52_f64(torch::Tensor x1, torch::Tensor x2,
   return out;
 }
 
-std::vector<torch::Tensor> eagle_suggest_f64(
-    torch::Tensor pool_cont, torch::Tensor pool_cat, torch::Tensor rewards,
-    torch::Tensor perturbations, torch::Tensor cat_sizes,
-    torch::Tensor iter_counter, int64_t n_batches, int64_t batch_size,
-    double visibility, double gravity, double neg_gravity,
-    double norm_scale, double cat_factor, double p_same, int64_t seed,
-    torch::Tensor out_cont, torch::Tensor out_cat, int64_t max_cat) {
-  const EagleShape s = check_eagle_suggest_args(
-      pool_cont, pool_cat, rewards, perturbations, cat_sizes, iter_counter,
-      n_batches, batch_size, out_cont, out_cat, max_cat, torch::kFloat64);
-  launch_eagle_suggest_f64(
-      pool_cont.data_ptr<double>(),
-      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
-      rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
-      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
-      out_cont.data_ptr<double>(),
-      s.dcat ? out_cat.data_ptr<long>() : nullptr,
-      (const unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, s.batch_size, s.pool_size, s.q, s.dc, s.dcat,
-      (int)max_cat, visibility, gravity, neg_gravity, norm_scale,
-      cat_factor, p_same, (unsigned long long)seed, current_stream());
-  return {out_cont, out_cat};
-}
-
-void eagle_update_f64(torch::Tensor pool_cont, torch::Tensor pool_cat,
-                      torch::Tensor rewards, torch::Tensor perturbations,
-                      torch::Tensor batch_cont, torch::Tensor batch_cat,
-                      torch::Tensor batch_rewards, torch::Tensor cat_sizes,
-                      torch::Tensor best_reward, torch::Tensor iter_counter,
-                      int64_t n_batches, double penalize_factor,
-                      double perturbation_lower_bound,
-                      double base_perturbation, int64_t seed) {
-  const EagleShape s = check_eagle_update_args(
-      pool_cont, pool_cat, rewards, perturbations, batch_cont, batch_cat,
-      batch_rewards, cat_sizes, best_reward, iter_counter, n_batches,
-      torch::kFloat64);
-  launch_eagle_update_f64(
-      pool_cont.data_ptr<double>(),
-      s.dcat ? pool_cat.data_ptr<long>() : nullptr,
-      rewards.data_ptr<double>(), perturbations.data_ptr<double>(),
-      batch_cont.data_ptr<double>(),
-      s.dcat ? batch_cat.data_ptr<long>() : nullptr,
-      batch_rewards.data_ptr<double>(),
-      s.dcat ? cat_sizes.data_ptr<long>() : nullptr,
-      best_reward.data_ptr<double>(),
-      (unsigned long long*)iter_counter.data_ptr<int64_t>(),
-      (int)n_batches, s.batch_size, s.q, s.dc, s.dcat, penalize_factor,
-      perturbation_lower_bound, base_perturbation,
-      (unsigned long long)seed, current_stream());
-}
-
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1663,9 +1636,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp64 fused (mean, sd, dist) over candidates (gfx950)");
   m.def("gram_matern52_f64", &gram_matern52_f64,
         "fp64 difference-form Matern-5/2 Gram / cross-Gram (gfx950)");
-  m.def("eagle_suggest_f64", &eagle_suggest_f64,
+  m.def("eagle_suggest_f64", eagle_suggest_f64,
         "fp64 fused Eagle suggest step (gfx950)");
-  m.def("eagle_update_f64", &eagle_update_f64,
+  m.def("eagle_update_f64", eagle_update_f64,
         "fp64 fused Eagle update step (gfx950)");
   m.def("gram_matern52_batched", &gram_matern52_batched,
         "Batched-restart fused Matern-5/2 gram (+noise*I, optional "
@@ -1721,9 +1694,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused GP-UCB-PE set-PE scorer: explore (mean, sd), joint "
         "covariance under the completed + pending posterior, logdet tail; "
         "stream-capturable (gfx950)");
-  m.def("eagle_suggest", &eagle_suggest,
+  m.def("eagle_suggest", eagle_suggest,
         "Fused Eagle suggest step (gfx950)");
-  m.def("eagle_update", &eagle_update, "Fused Eagle update step (gfx950)");
+  m.def("eagle_update", eagle_update, "Fused Eagle update step (gfx950)");
   m.def("eagle_sweep", &eagle_sweep,
         "Persistent cooperative Eagle sweep megakernel (gfx950)");
 }

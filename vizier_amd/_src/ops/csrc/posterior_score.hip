@@ -23,21 +23,6 @@
 #define BLOCK 256
 #define MAX_N_LDS 8192  // 32 KiB of k[] in LDS
 
-// acquisition codes
-#define ACQ_UCB 0
-#define ACQ_LCB 1
-#define ACQ_EI 2
-#define ACQ_PI 3
-#define ACQ_MEAN 4
-#define ACQ_STDDEV 5
-
-__device__ __forceinline__ float normal_cdf(float z) {
-  return 0.5f * erfcf(-z * 0.70710678118654752f);
-}
-__device__ __forceinline__ float normal_pdf(float z) {
-  return 0.3989422804014327f * __expf(-0.5f * z * z);
-}
-
 extern "C" __global__ __launch_bounds__(BLOCK) void
 posterior_score_kernel(const float* __restrict__ xq,     // (B, D)
                        const float* __restrict__ x,      // (N, D)
@@ -111,28 +96,8 @@ posterior_score_kernel(const float* __restrict__ xq,     // (B, D)
     mu += mean_c;
     var = fmaxf(amp2 - var, 1e-12f);
     const float sd = sqrtf(var);
-    float score;
-    switch (acq) {
-      case ACQ_LCB: score = mu - coef * sd; break;
-      case ACQ_EI: {
-        const float z = (mu - best_value) / sd;
-        score = sd * (z * normal_cdf(z) + normal_pdf(z));
-        break;
-      }
-      case ACQ_PI: {
-        const float z = (mu - best_value) / sd;
-        score = normal_cdf(z);
-        break;
-      }
-      case ACQ_MEAN: score = mu; break;
-      case ACQ_STDDEV: score = sd; break;
-      case ACQ_UCB:
-      default: score = mu + coef * sd; break;
-    }
-    if (tr_radius > 0.0f && tr_radius <= 0.5f && dist > tr_radius) {
-      score = -1e4f - dist;
-    }
-    out[q] = score;
+    const float score = vz_acq_score(acq, mu, sd, coef, best_value);
+    out[q] = vz_trust_region(score, dist, tr_radius);
   }
 }
 
@@ -273,29 +238,8 @@ ps_finalize_kernel(const float* __restrict__ mu_in,
   var = fmaxf(amp2 - var, 1e-12f);
   const float sd = sqrtf(var);
   const float mu = mu_in[q] + mean_c;
-  float score;
-  switch (acq) {
-    case ACQ_LCB: score = mu - coef * sd; break;
-    case ACQ_EI: {
-      const float z = (mu - best_value) / sd;
-      score = sd * (z * normal_cdf(z) + normal_pdf(z));
-      break;
-    }
-    case ACQ_PI: {
-      const float z = (mu - best_value) / sd;
-      score = normal_cdf(z);
-      break;
-    }
-    case ACQ_MEAN: score = mu; break;
-    case ACQ_STDDEV: score = sd; break;
-    case ACQ_UCB:
-    default: score = mu + coef * sd; break;
-  }
-  const float dist = dist_in[q];
-  if (tr_radius > 0.0f && tr_radius <= 0.5f && dist > tr_radius) {
-    score = -1e4f - dist;
-  }
-  out[q] = score;
+  const float score = vz_acq_score(acq, mu, sd, coef, best_value);
+  out[q] = vz_trust_region(score, dist_in[q], tr_radius);
 }
 
 // -- bf16 k-vector with CACHED training operands ------------------------
@@ -880,29 +824,8 @@ ps_finalize_direct_kernel(const float* __restrict__ mu_in,
   float var = fmaxf(amp2 - quad_in[q], 1e-12f);
   const float sd = sqrtf(var);
   const float mu = mu_in[q] + mean_c;
-  float score;
-  switch (acq) {
-    case ACQ_LCB: score = mu - coef * sd; break;
-    case ACQ_EI: {
-      const float z = (mu - best_value) / sd;
-      score = sd * (z * normal_cdf(z) + normal_pdf(z));
-      break;
-    }
-    case ACQ_PI: {
-      const float z = (mu - best_value) / sd;
-      score = normal_cdf(z);
-      break;
-    }
-    case ACQ_MEAN: score = mu; break;
-    case ACQ_STDDEV: score = sd; break;
-    case ACQ_UCB:
-    default: score = mu + coef * sd; break;
-  }
-  const float dist = dist_in[q];
-  if (tr_radius > 0.0f && tr_radius <= 0.5f && dist > tr_radius) {
-    score = -1e4f - dist;
-  }
-  out[q] = score;
+  const float score = vz_acq_score(acq, mu, sd, coef, best_value);
+  out[q] = vz_trust_region(score, dist_in[q], tr_radius);
 }
 
 extern "C" void launch_ps_kvec(

@@ -28,16 +28,9 @@
 // fixed xor-shuffle tree, one partial per (q, column tile, slab).
 
 #include <hip/hip_runtime.h>
-#include "common_f64.h"
+#include "common.h"
 
 #define BLOCK 256
-
-#define ACQ_UCB 0
-#define ACQ_LCB 1
-#define ACQ_EI 2
-#define ACQ_PI 3
-#define ACQ_MEAN 4
-#define ACQ_STDDEV 5
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
@@ -71,17 +64,17 @@ ps_kvec_f64_kernel(const double* __restrict__ xq,      // (B, D)
       d2 = fma(z, z, d2);
       if (!onehot[j]) linf = fmax(linf, fabs(diff));
     }
-    const double kv = amp2 * vz_matern52_of_d2_f64(d2);
+    const double kv = amp2 * matern52_of_d2(d2);
     k_out[(long)q * n + row] = kv;
     mu_acc = fma(kv, alpha[row], mu_acc);
     min_linf = fmin(min_linf, linf);
   }
   auto dsum = [](double a, double c) { return a + c; };
   auto dmin = [](double a, double c) { return fmin(a, c); };
-  const double mu = block_reduce_f64(mu_acc, red, dsum, 0.0);
+  const double mu = block_reduce(mu_acc, red, dsum, 0.0);
   if (tid == 0) mu_out[q] = mu;
   __syncthreads();
-  const double dist = block_reduce_f64(min_linf, red, dmin, (double)INFINITY);
+  const double dist = block_reduce(min_linf, red, dmin, (double)INFINITY);
   if (tid == 0) dist_out[q] = dist;
 }
 
@@ -196,7 +189,7 @@ ps_finalize_f64_kernel(const double* __restrict__ mu_in,
   double acc = 0.0;
   for (long t = tid; t < nparts; t += BLOCK) acc += p[t];
   auto dsum = [](double a, double c) { return a + c; };
-  const double quad = block_reduce_f64(acc, red, dsum, 0.0);
+  const double quad = block_reduce(acc, red, dsum, 0.0);
   if (tid != 0) return;
   const double var = fmax(amp2 - quad, 1e-12);
   const double sd = sqrt(var);
@@ -204,29 +197,8 @@ ps_finalize_f64_kernel(const double* __restrict__ mu_in,
   if (mean_out != nullptr) mean_out[q] = mu;
   if (sd_out != nullptr) sd_out[q] = sd;
   if (out == nullptr) return;
-  double score;
-  switch (acq) {
-    case ACQ_LCB: score = mu - coef * sd; break;
-    case ACQ_EI: {
-      const double z = (mu - best_value) / sd;
-      score = sd * (z * vz_normal_cdf_f64(z) + vz_normal_pdf_f64(z));
-      break;
-    }
-    case ACQ_PI: {
-      const double z = (mu - best_value) / sd;
-      score = vz_normal_cdf_f64(z);
-      break;
-    }
-    case ACQ_MEAN: score = mu; break;
-    case ACQ_STDDEV: score = sd; break;
-    case ACQ_UCB:
-    default: score = mu + coef * sd; break;
-  }
-  const double dist = dist_in[q];
-  if (tr_radius > 0.0 && tr_radius <= 0.5 && dist > tr_radius) {
-    score = -1e4 - dist;
-  }
-  out[q] = score;
+  const double score = vz_acq_score(acq, mu, sd, coef, best_value);
+  out[q] = vz_trust_region(score, dist_in[q], tr_radius);
 }
 
 // -- launcher --------------------------------------------------------------------

@@ -50,7 +50,7 @@ def require_ext():
 
 def fp64_hip_enabled() -> bool:
   """True iff VIZIER_AMD_FP64_HIP=1: float64 GPU tensors take the fp64 HIP
-  kernels (posterior_score_f64 / gram_matern52_f64 / eagle_step_f64).
+  kernels (posterior_score_f64 / gram_matern52_f64 / eagle_step<double>).
 
   Opt-in, default off: the fp64 Eagle kernels draw a different RNG stream
   than the torch fp64 path, so suggestions change when it is switched on.

@@ -119,6 +119,7 @@ def probe_d():
   cfg = strategy.config
 
   def run(iters):
+    barrier_buf.zero_()  # the barrier counts up from zero over one launch
     return ext.eagle_sweep(
         state.continuous, state.rewards, state.perturbations,
         state.best_reward.reshape(1), strategy._iter_t, barrier_buf,

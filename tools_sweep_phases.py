@@ -42,7 +42,11 @@ opt.optimize(score_fn, count=1)
 torch.cuda.synchronize()
 wall = time.perf_counter() - t0
 delta = (strat._iter_t[2:12] - base).cpu().numpy().astype(float)
-names = ['A', 'barA', 'B', 'barB', 'B2', 'barB2', 'C', 'barC',
+# Slots of eagle_sweep.hip. At the headline shape the kernel runs resident
+# and folded: A, barA, B, barB, RC per iteration; B2 / barB2 (only above
+# 1024 tiles) and barC (only when pool * dc > 4096) stay 0. 'RC' is the
+# legacy phase C in that mode.
+names = ['A', 'barA', 'B', 'barB', 'B2', 'barB2', 'RC', 'barC',
          'B.stage', 'B.main']
 total = delta[:8].sum()
 iters = 3000 - (strat.pool_size // strat.batch_size + 2)
@@ -50,3 +54,5 @@ print(f'sweep wall: {wall*1e3:.1f} ms over ~{iters} megakernel iters '
       f'({wall/3000*1e6:.1f} us/iter incl. eager head)')
 for nm, c in zip(names, delta):
   print(f'  {nm:6s} {c/total*100:5.1f}%  {c/iters:10.0f} cyc/iter')
+bars = delta[[1, 3, 5, 7]].sum()
+print(f'  barriers {bars/total*100:5.1f}%  {bars/iters:10.0f} cyc/iter')

@@ -194,6 +194,8 @@ class VectorizedOptimizer:
       # (the megakernel's phase B/B2 layout; see eagle_sweep.hip).
       var_ws = _torch.empty(b, tiles_n * tiles_n + 1,
                             dtype=_torch.float32, device=dev)
+      # Zeroed per call: the kernel's grid barrier counts arrivals upwards
+      # from zero over one launch.
       barrier_buf = _torch.zeros(2, dtype=_torch.int32, device=dev)
       from vizier_amd._src.ops import dispatch as ops
       amp2 = scoring._amp * scoring._amp

@@ -15,12 +15,61 @@
 //     loads/stores — coherent at the memory side, no cache flush;
 //   - keeps the heavy read-only data (K^-1, x, alpha) on the normal
 //     cached path (L2-resident across all iterations);
-//   - uses a hand-rolled sense-reversing grid barrier on agent-scope
-//     atomics (s_waitcnt vmcnt(0) before arrival orders the relaxed
-//     data stores), 3 barriers per iteration;
+//   - uses a hand-rolled grid barrier on ONE agent-scope counter that
+//     only grows (grid_sync below; s_waitcnt 0 before arrival orders the
+//     relaxed data stores);
 //   - merges phases so a single workgroup owns candidate b through
-//     suggest+k-vec (A) and finalize+update (C); only the quadform (B)
-//     fans out across the grid.
+//     suggest+k-vec (A); only the quadform (B) fans out across the grid.
+//
+// Phases and grid barriers per iteration. Two grid-uniform switches pick
+// among four forms:
+//   resident  pool_size * dc <= RESIDENT_CAP (4096 floats)
+//   folded    tile partials T <= FOLD_MAX_TILES (1024, i.e. N <= 2048)
+//
+//   resident, folded  (flagship)   A | B | RC                 2 barriers
+//   resident, not folded           A | B | B2 | RC            3 barriers
+//   legacy, folded                 A | B | C |                3 barriers
+//   legacy, not folded             A | B | B2 | C |           4 barriers
+//
+// Folded: B2 and its barrier existed to hand 25 floats over. Every
+// workgroup that runs C / RC needs all scores anyway, so it reduces the
+// partials of all candidates itself, in B2's exact order
+// (reduce_all_partials), and the owner of candidate q still stores the
+// reduced value to var_ws[q, T] for the caller.
+//
+// Resident: every workgroup that owns a candidate (blockIdx.x <
+// batch_size) loads pool, rewards, perturbations and best_reward once at
+// kernel start into LDS (the upper half of pool_lds, which phase B's
+// k_i / k_j staging does not touch, plus st_rewards / st_perts / st_best)
+// and keeps them for the whole launch. RC = reduce + scores + update:
+// each owner applies the update of ALL batch_size fireflies, with the
+// logic and RNG indices of the legacy phase C, to its own copy. The
+// inputs (all scores, all candidates, the old state) are the same for
+// every owner, so the copies stay identical, nobody reads another's
+// state, and the next A follows RC with no grid barrier and no restaging
+// of the pool. After the last iteration workgroup 0 stores its copy back.
+// Workgroups that own no candidate skip A and RC. With a grid below the
+// batch, A loops over its candidates and RC runs once per workgroup.
+//
+// Parity scratch (resident mode). With no barrier after RC, a fast
+// workgroup's A(it+1) would overwrite candidate, mu and dist of its row
+// while a slow one still reads them in RC(it). So A(it) also writes them
+// to slot it & 1 of slot_ws (2 x batch x (dc + 2) floats, allocated by
+// the binding, cstore) and RC(it) reads only that slot (cload). This is
+// race-free by construction, not by timing: A(it+1) writes the OTHER
+// slot; the next writer of slot it & 1 is A(it+2), and a workgroup gets
+// there only through barrier A|B of it+1, at which every workgroup has
+// arrived only after finishing its RC(it). The caller-visible out_cont,
+// mu_ws and dist_ws are still written by A, for the tests; nothing in
+// resident mode reads them. k_ws and the tile partials are written and
+// read only across the barriers that remain (A|B and B|RC), and
+// var_ws[q, T] is written by one owner and read by no one when folded.
+//
+// Legacy (pool_size * dc > RESIDENT_CAP): the state lives in global
+// memory behind cload / cstore, A stages the pool in LDS per iteration up
+// to POOL_LDS_CAP floats and reads it through cload above, the owner of
+// candidate i updates firefly i in C, and a barrier separates C from the
+// next A.
 //
 // Scope: continuous-only spaces, q == 1 (the flagship GP-Bandit
 // config); the optimizer falls back to the hipGraph path otherwise.
@@ -51,6 +100,9 @@
 #define MAX_POOL 128
 #define SWEEP_NCHUNK 10   // must match posterior_score.hip's NCHUNK
 #define POOL_LDS_CAP 8192  // floats: stage pool in LDS when it fits
+// floats: at or below this the pool lives in the upper half of pool_lds
+// for the whole launch (phase B stages k_i / k_j in the lower half only).
+#define RESIDENT_CAP (POOL_LDS_CAP / 2)
 
 // Agent-scope (device) coherent access helpers: compile to memory-side
 // accesses that bypass the incoherent per-XCD L2 path for plain loads.
@@ -61,8 +113,20 @@ __device__ __forceinline__ void cstore(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Sense-reversing grid barrier on agent-scope atomics. bar[0] = arrival
-// count, bar[1] = generation.
+// Grid barrier on ONE agent-scope counter that only grows. bar[0] counts
+// arrivals over the whole launch and is zeroed by the caller before every
+// launch; bar[1] is unused. The k-th barrier of the launch (k = 0, 1, ...)
+// is complete once bar[0] >= (k + 1) * G. Every workgroup keeps
+// `target` = (k + 1) * G in a register and advances it identically, so a
+// barrier is one fetch_add plus polls of the same word: two dependent
+// memory-side round trips, where the sense-reversing form it replaced took
+// about five (generation load, fetch_add, reset store, waitcnt,
+// generation fetch_add, then the pollers' load). A fast workgroup that
+// arrives at barrier k + 1 while a slow one still polls barrier k only
+// pushes the count further past the slow one's target, and the count
+// cannot reach (k + 2) * G before everyone has arrived at k + 1. The
+// compare is on the signed difference, so wrap-around of the counter is
+// harmless.
 //
 // Deliberately RELAXED atomics: acq_rel orderings compile to
 // buffer_wbl2 / buffer_inv (full per-XCD L2 writeback+invalidate),
@@ -77,31 +141,95 @@ __device__ __forceinline__ void cstore(float* p, float v) {
 //     cache invalidation is needed on the acquire side;
 //   - waves issue memory ops in order, so the spin-exit load ordering
 //     is sufficient (compiler reordering is fenced with asm).
-__device__ __forceinline__ void grid_sync(unsigned int* bar) {
+__device__ __forceinline__ void grid_sync(unsigned int* bar,
+                                          unsigned int& target) {
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
+  target += gridDim.x;
   if (threadIdx.x == 0) {
-    const unsigned int gen =
-        __hip_atomic_load(bar + 1, __ATOMIC_RELAXED,
-                          __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("" ::: "memory");
-    const unsigned int arrived = __hip_atomic_fetch_add(
-        bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (arrived == gridDim.x - 1) {
-      __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_s_waitcnt(0);  // count reset lands before gen++
-      __hip_atomic_fetch_add(bar + 1, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      while (__hip_atomic_load(bar + 1, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT) == gen) {
+    // The value the fetch_add returns already tells the last arriver
+    // that the barrier is complete.
+    const unsigned int count = __hip_atomic_fetch_add(
+        bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    if ((int)(count - target) < 0) {
+      while ((int)(__hip_atomic_load(bar, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT) -
+                   target) < 0) {
         __builtin_amdgcn_s_sleep(8);
       }
     }
     asm volatile("" ::: "memory");
   }
   __syncthreads();
+}
+
+// Tile partials at or below which phase C reduces them itself (N <= 2048:
+// at most 4 loads per candidate per thread). Above it the redundant read
+// grows with N^2 and phase B2 with its barrier stays.
+#define FOLD_MAX_TILES 1024
+
+// Reduces the tile partials of ALL candidates at once, in phase B2's exact
+// order: thread tid adds w = tid, tid + 256, ... sequentially, then the
+// shuffle tree of block_reduce runs per candidate. Wave v leaves
+// candidate q's wave partial in wp[v * VZ_QF_QMAX + q]; after ONE
+// __syncthreads, fold_quad(wp, q) is bit for bit what B2 stores. The loads
+// of a trip are issued together (rows past the batch re-read its last
+// row, so the unrolled loop has no branch that would wait per candidate).
+__device__ __forceinline__ void reduce_all_partials(
+    const float* var_ws, int batch_size, int total_tiles, float* wp) {
+  const int tid = threadIdx.x;
+  float sacc[VZ_QF_QMAX];
+#pragma unroll
+  for (int q = 0; q < VZ_QF_QMAX; ++q) sacc[q] = 0.0f;
+  for (int w0 = 0; w0 < total_tiles; w0 += BLOCK) {
+    const int w = w0 + tid;
+    const bool live = w < total_tiles;
+    const int wc = live ? w : total_tiles - 1;
+    float v[VZ_QF_QMAX];
+#pragma unroll
+    for (int q = 0; q < VZ_QF_QMAX; ++q) {
+      const int qc = min(q, batch_size - 1);
+      v[q] = cload(var_ws + (long)qc * (total_tiles + 1) + wc);
+    }
+#pragma unroll
+    for (int q = 0; q < VZ_QF_QMAX; ++q) {
+      sacc[q] = live ? sacc[q] + v[q] : sacc[q];
+    }
+  }
+  // The shuffle tree of block_reduce, for all VZ_QF_QMAX candidates in 32
+  // shuffles where one tree each would take 6 x 32. A tree level with
+  // offset `off` computes v[p] + v[p + off] for positions p < off and
+  // nothing else reaches lane 0, so half the lanes of every level are
+  // idle: level `off` packs two registers into one, the lanes with
+  // (lane & off) == 0 doing the first register's adds and the others the
+  // second's. Each add has the operands of the original tree (swapped in
+  // the upper lanes; fp add commutes), so the sums are bit-identical.
+  // After the off = 2 level one register holds candidate q at the lanes
+  // 2 * bitreverse5(q) + {0, 1}; the last level adds the pair.
+  const int lane = tid & (WAVE_SIZE - 1);
+#pragma unroll
+  for (int off = WAVE_SIZE / 2; off > 1; off >>= 1) {
+    const bool up = (lane & off) != 0;
+#pragma unroll
+    for (int i = 0; i < off / 2; ++i) {
+      const float keep = up ? sacc[2 * i + 1] : sacc[2 * i];
+      const float send = up ? sacc[2 * i] : sacc[2 * i + 1];
+      sacc[i] = keep + __shfl_xor(send, off, WAVE_SIZE);
+    }
+  }
+  const float total = sacc[0] + __shfl_xor(sacc[0], 1, WAVE_SIZE);
+  if ((lane & 1) == 0) {
+    const int q = (int)(__brev((unsigned)(lane >> 1)) >> 27);
+    wp[(tid / WAVE_SIZE) * VZ_QF_QMAX + q] = total;
+  }
+}
+
+// block_reduce's second stage over the 4 wave partials: lanes 0..3 hold
+// v0..v3, shuffle offsets 2 then 1 give (v0 + v2) + (v1 + v3).
+__device__ __forceinline__ float fold_quad(const float* wp, int q) {
+  return (wp[q] + wp[2 * VZ_QF_QMAX + q]) +
+         (wp[VZ_QF_QMAX + q] + wp[3 * VZ_QF_QMAX + q]);
 }
 
 extern "C" __global__ __launch_bounds__(BLOCK) void
@@ -120,7 +248,8 @@ eagle_sweep_kernel(
     float* __restrict__ k_ws,              // (B, N)    [coherent]
     float* __restrict__ mu_ws,             // (B,)      [coherent]
     float* __restrict__ dist_ws,           // (B,)      [coherent]
-    float* __restrict__ var_ws,            // (B, NCHUNK) [coherent]
+    float* __restrict__ var_ws,            // (B, T+1)  [coherent]
+    float* __restrict__ slot_ws,           // (2, B*(Dc+2)) [coherent]
     int n_batches, int batch_size, int pool_size, int dc, int n,
     long long it_start, long long iterations,
     float visibility, float gravity, float neg_gravity, float norm_scale,
@@ -134,21 +263,34 @@ eagle_sweep_kernel(
   __shared__ float s_scalar;
   __shared__ float xq_lds[512];
   __shared__ float pool_lds[POOL_LDS_CAP];
+  // Resident mode: this workgroup's private copy of the Eagle state.
+  __shared__ float st_rewards[MAX_POOL];
+  __shared__ float st_perts[MAX_POOL];
+  __shared__ float st_best;
 
   const int tid = threadIdx.x;
   const int G = gridDim.x;
   const int pool_elems = pool_size * dc;
-  const bool stage_pool = pool_elems <= POOL_LDS_CAP;
+  // All three are grid-uniform: every workgroup takes the same barriers.
+  const bool resident = pool_elems <= RESIDENT_CAP;
+  const bool stage_pool = !resident && pool_elems <= POOL_LDS_CAP;
+  const bool pool_in_lds = resident || stage_pool;
+  const bool owner = blockIdx.x < batch_size;
+  float* st_pool = pool_lds + RESIDENT_CAP;
+  const float* pl = resident ? st_pool : pool_lds;
   auto fsum = [](float a, float c) { return a + c; };
   auto fmin_ = [](float a, float c) { return fminf(a, c); };
   auto fmax_ = [](float a, float c) { return fmaxf(a, c); };
 
   // Per-phase cycle profiling (workgroup 0's view, including its
   // barrier-wait slack): accumulated into iter_ptr[2..9] as
-  // A, barA, B, barB, B2, barB2, C, barC. Reads are a handful of
-  // s_memtime per iteration on one lane — no measurable perturbation.
+  // A, barA, B, barB, B2, barB2, RC (legacy: C), barC. A phase or
+  // barrier the mode does not take leaves its slot untouched: B2 / barB2
+  // when folded, barC when resident. Reads are a handful of s_memtime
+  // per iteration on one lane — no measurable perturbation.
   const bool profwg = (blockIdx.x == 0 && threadIdx.x == 0);
   unsigned long long tmark = profwg ? wall_clock64() : 0;
+  unsigned int bar_target = 0;  // (barriers passed) * G, see grid_sync
 #define VZ_SWEEP_PROF(slot)                                        \
   if (profwg) {                                                    \
     const unsigned long long tnow = wall_clock64();                \
@@ -156,8 +298,24 @@ eagle_sweep_kernel(
     tmark = tnow;                                                  \
   }
 
+  // Resident mode: the state was written by earlier launches, so plain
+  // loads see it; from here on only this workgroup touches its copy.
+  if (resident && owner) {
+    for (int e = tid; e < pool_elems; e += BLOCK) st_pool[e] = pool_cont[e];
+    for (int p = tid; p < pool_size; p += BLOCK) {
+      st_rewards[p] = rewards[p];
+      st_perts[p] = perturbations[p];
+    }
+    if (tid == 0) st_best = best_reward[0];
+    __syncthreads();
+  }
+
   for (long long it = it_start; it < it_start + iterations; ++it) {
     const unsigned long long offset = (unsigned long long)it;
+    // Parity slot of this iteration: candidates, then mu, then dist.
+    float* slot_c = slot_ws + (long)(it & 1) * batch_size * (dc + 2);
+    float* slot_mu = slot_c + batch_size * dc;
+    float* slot_dist = slot_mu + batch_size;
     const int batch_start =
         (int)(offset % (unsigned long long)n_batches) * batch_size;
     if (profwg) tmark = wall_clock64();
@@ -171,13 +329,15 @@ eagle_sweep_kernel(
         __syncthreads();
       }
       const int me = batch_start + b;
-      const float my_reward = cload(rewards + me);
-      const float my_pert = cload(perturbations + me);
+      const float my_reward = resident ? st_rewards[me]
+                                       : cload(rewards + me);
+      const float my_pert = resident ? st_perts[me]
+                                     : cload(perturbations + me);
       for (int p = tid; p < pool_size; p += BLOCK) {
         float d2 = 0.0f;
-        if (stage_pool) {
+        if (pool_in_lds) {
           for (int j = 0; j < dc; ++j) {
-            const float diff = pool_lds[me * dc + j] - pool_lds[p * dc + j];
+            const float diff = pl[me * dc + j] - pl[p * dc + j];
             d2 = fmaf(diff, diff, d2);
           }
         } else {
@@ -187,7 +347,8 @@ eagle_sweep_kernel(
             d2 = fmaf(diff, diff, d2);
           }
         }
-        const float reward_p = cload(rewards + p);
+        const float reward_p = resident ? st_rewards[p]
+                                        : cload(rewards + p);
         const float dir = (reward_p - my_reward >= 0.0f) ? gravity
                                                          : -neg_gravity;
         const float force = __expf(-visibility * d2 / dc * 10.0f);
@@ -224,23 +385,24 @@ eagle_sweep_kernel(
       scale_sum = s_scalar;
       for (int j = tid; j < dc; j += BLOCK) {
         float moved = 0.0f;
-        if (stage_pool) {
+        if (pool_in_lds) {
           for (int p = 0; p < pool_size; ++p) {
-            moved = fmaf(scale[p], pool_lds[p * dc + j], moved);
+            moved = fmaf(scale[p], pl[p * dc + j], moved);
           }
         } else {
           for (int p = 0; p < pool_size; ++p) {
             moved = fmaf(scale[p], cload(pool_cont + p * dc + j), moved);
           }
         }
-        const float mine = stage_pool ? pool_lds[me * dc + j]
-                                      : cload(pool_cont + me * dc + j);
+        const float mine = pool_in_lds ? pl[me * dc + j]
+                                       : cload(pool_cont + me * dc + j);
         moved = mine + (moved - mine * scale_sum);
         float noise = vz_rng_laplace<float>(seed_suggest, offset,
                                      (unsigned)(b * dc + j));
         noise = (noise >= 0.0f) ? 1.0f : -1.0f;  // q == 1
         const float cand = moved + noise * my_pert;
         out_cont[b * dc + j] = cand;
+        if (resident) cstore(slot_c + b * dc + j, cand);
         xq_lds[j] = cand;
       }
       __syncthreads();
@@ -263,14 +425,20 @@ eagle_sweep_kernel(
         min_linf = fminf(min_linf, linf);
       }
       float mu = block_reduce(mu_acc, red, fsum, 0.0f);
-      if (tid == 0) cstore(mu_ws + b, mu);
+      if (tid == 0) {
+        cstore(mu_ws + b, mu);
+        if (resident) cstore(slot_mu + b, mu);
+      }
       __syncthreads();
       float dist = block_reduce(min_linf, red, fmin_, INFINITY);
-      if (tid == 0) cstore(dist_ws + b, dist);
+      if (tid == 0) {
+        cstore(dist_ws + b, dist);
+        if (resident) cstore(slot_dist + b, dist);
+      }
       __syncthreads();
     }
     VZ_SWEEP_PROF(0)
-    grid_sync(barrier_buf);
+    grid_sync(barrier_buf, bar_target);
     VZ_SWEEP_PROF(1)
 
     // ---- Phase B: K^-1 quadform (64x64 tiles, Kinv read ONCE) ----
@@ -296,94 +464,213 @@ eagle_sweep_kernel(
       }
     }
     VZ_SWEEP_PROF(2)
-    grid_sync(barrier_buf);
+    grid_sync(barrier_buf, bar_target);
     VZ_SWEEP_PROF(3)
 
     // ---- Phase B2: reduce tile partials (order == the standalone
-    // ps_reduce_parts_kernel) ----
-    {
-      const int tiles_n = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
-      const int total_tiles = tiles_n * tiles_n;
+    // ps_reduce_parts_kernel). Only above FOLD_MAX_TILES; below it
+    // phase C reduces them itself and this barrier is not taken. ----
+    const int tiles_n_c = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
+    const int total_tiles_c = tiles_n_c * tiles_n_c;
+    const bool fold = total_tiles_c <= FOLD_MAX_TILES;  // grid-uniform
+    if (!fold) {
       for (int q = blockIdx.x; q < batch_size; q += G) {
         float sacc = 0.0f;
-        for (int w = tid; w < total_tiles; w += BLOCK) {
-          sacc += cload(var_ws + (long)q * (total_tiles + 1) + w);
+        for (int w = tid; w < total_tiles_c; w += BLOCK) {
+          sacc += cload(var_ws + (long)q * (total_tiles_c + 1) + w);
         }
         float total = block_reduce(sacc, red, fsum, 0.0f);
         if (tid == 0) {
-          cstore(var_ws + (long)q * (total_tiles + 1) + total_tiles,
+          cstore(var_ws + (long)q * (total_tiles_c + 1) + total_tiles_c,
                  total);
         }
         __syncthreads();
       }
+      VZ_SWEEP_PROF(4)
+      grid_sync(barrier_buf, bar_target);
+      VZ_SWEEP_PROF(5)
     }
-    VZ_SWEEP_PROF(4)
-    grid_sync(barrier_buf);
-    VZ_SWEEP_PROF(5)
 
-    // ---- Phase C: finalize scores (inline) + update ----
-    for (int i = blockIdx.x; i < batch_size; i += G) {
-      // Every workgroup recomputes all B scores from the coherent
-      // partials (cheap, deterministic, removes a barrier).
-      float local_max = -INFINITY;
-      float my_score = -INFINITY;
-      const int tiles_n_c = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
-      const int total_tiles_c = tiles_n_c * tiles_n_c;
-      for (int t = tid; t < batch_size; t += BLOCK) {
-        const float quad =
-            cload(var_ws + (long)t * (total_tiles_c + 1) + total_tiles_c);
-        float var = fmaxf(amp2 - quad, 1e-12f);
-        const float sd = sqrtf(var);
-        const float mu = cload(mu_ws + t) + mean_c;
-        const float score = vz_trust_region(
-            vz_acq_score(acq, mu, sd, coef, best_value),
-            cload(dist_ws + t), tr_radius);
-        local_max = fmaxf(local_max, score);
-        if (t == i) my_score = score;
-      }
-      float batch_max = block_reduce(local_max, red, fmax_, -INFINITY);
-      // my_score lives in the thread with tid == i%BLOCK (B <= BLOCK):
-      // broadcast through LDS.
-      if (tid == (i % BLOCK) && i < BLOCK) red[6] = my_score;
-      __syncthreads();
-      const float new_r = red[6];
-      if (tid == 0) {
-        s_scalar = fmaxf(cload(best_reward), batch_max);
-        if (i == 0) cstore(best_reward, s_scalar);
-      }
-      __syncthreads();
-      const float new_best = s_scalar;
-      const int me = batch_start + i;
-      const float old_r = cload(rewards + me);
-      const bool improved = new_r > old_r;
-      const float old_pert = cload(perturbations + me);
-      float pert = improved ? old_pert : old_pert * penalize_factor;
-      float reward = improved ? new_r : old_r;
-      const bool dead = (pert < perturbation_lower_bound) &&
-                        (reward != new_best);
-      if (improved) {
-        for (int j = tid; j < dc; j += BLOCK) {
-          cstore(pool_cont + me * dc + j, out_cont[i * dc + j]);
+    // ---- Phase C / RC: reduce (when folded) + scores + update ----
+    // Scratch in phase B's staging area, free until the next phase B:
+    // 4 x VZ_QF_QMAX wave partials, then VZ_QF_QMAX scores.
+    float* wp = pool_lds;
+    float* sc_lds = pool_lds + 4 * VZ_QF_QMAX;
+    auto score_of = [&](float quad, float mu_raw, float dist) {
+      float var = fmaxf(amp2 - quad, 1e-12f);
+      const float sd = sqrtf(var);
+      const float mu = mu_raw + mean_c;
+      return vz_trust_region(vz_acq_score(acq, mu, sd, coef, best_value),
+                             dist, tr_radius);
+    };
+    if (resident) {
+      // RC: every owning workgroup applies the update of ALL fireflies
+      // of the batch to its own LDS copy of the state, with the logic and
+      // RNG indices of the legacy phase C below, and goes straight on to
+      // the next phase A: no grid barrier.
+      if (owner) {
+        float mu_t = 0.0f, dist_t = 0.0f;
+        if (tid < batch_size) {
+          mu_t = cload(slot_mu + tid);
+          dist_t = cload(slot_dist + tid);
         }
-      }
-      if (dead) {
-        for (int j = tid; j < dc; j += BLOCK) {
-          cstore(pool_cont + me * dc + j,
-                 vz_rng_uniform<float>(seed_update, offset ^ 0x5151ull,
-                                (unsigned)(me * dc + j)));
+        if (fold) {
+          reduce_all_partials(var_ws, batch_size, total_tiles_c, wp);
         }
-        reward = -INFINITY;
-        pert = base_perturbation;
+        __syncthreads();
+        if (tid < WAVE_SIZE) {  // batch <= VZ_QF_QMAX < WAVE_SIZE
+          float score = -INFINITY;
+          if (tid < batch_size) {
+            float* reduced =
+                var_ws + (long)tid * (total_tiles_c + 1) + total_tiles_c;
+            float quad;
+            if (fold) {
+              quad = fold_quad(wp, tid);
+              // The owner of candidate tid publishes the reduced value.
+              if (tid % G == (int)blockIdx.x) cstore(reduced, quad);
+            } else {
+              quad = cload(reduced);
+            }
+            score = score_of(quad, mu_t, dist_t);
+            sc_lds[tid] = score;
+          }
+          // block_reduce's max over the batch: waves 1..3 would only
+          // contribute -inf.
+          const float batch_max = wave_reduce_max(score);
+          if (tid == 0) s_scalar = fmaxf(st_best, batch_max);
+        }
+        __syncthreads();
+        const float new_best = s_scalar;
+        for (int e = tid; e < batch_size * dc; e += BLOCK) {
+          const int i = e / dc;
+          const int me = batch_start + i;
+          const int ej = me * dc + (e - i * dc);
+          const float new_r = sc_lds[i];
+          const float old_r = st_rewards[me];
+          const bool improved = new_r > old_r;
+          const float old_pert = st_perts[me];
+          const float pert = improved ? old_pert
+                                      : old_pert * penalize_factor;
+          const float reward = improved ? new_r : old_r;
+          const bool dead = (pert < perturbation_lower_bound) &&
+                            (reward != new_best);
+          if (dead) {
+            st_pool[ej] = vz_rng_uniform<float>(
+                seed_update, offset ^ 0x5151ull, (unsigned)ej);
+          } else if (improved) {
+            st_pool[ej] = cload(slot_c + e);
+          }
+        }
+        __syncthreads();  // every read of the old rewards / perts is done
+        if (tid < batch_size) {
+          const int me = batch_start + tid;
+          const float new_r = sc_lds[tid];
+          const float old_r = st_rewards[me];
+          const bool improved = new_r > old_r;
+          const float old_pert = st_perts[me];
+          float pert = improved ? old_pert : old_pert * penalize_factor;
+          float reward = improved ? new_r : old_r;
+          const bool dead = (pert < perturbation_lower_bound) &&
+                            (reward != new_best);
+          if (dead) {
+            reward = -INFINITY;
+            pert = base_perturbation;
+          }
+          st_rewards[me] = reward;
+          st_perts[me] = pert;
+        }
+        if (tid == 0) st_best = new_best;
+        __syncthreads();
       }
-      if (tid == 0) {
-        cstore(rewards + me, reward);
-        cstore(perturbations + me, pert);
+      VZ_SWEEP_PROF(6)
+    } else {
+      // Legacy: the state lives in global memory, the owner of candidate
+      // i updates firefly i, and a grid barrier separates C from the
+      // next A. Folded: an owning workgroup reduces the partials of all
+      // candidates once.
+      if (fold && owner) {
+        reduce_all_partials(var_ws, batch_size, total_tiles_c, wp);
+        __syncthreads();
       }
-      __syncthreads();
+      for (int i = blockIdx.x; i < batch_size; i += G) {
+        // Every workgroup recomputes all B scores from the coherent
+        // partials (cheap, deterministic, removes a barrier).
+        float local_max = -INFINITY;
+        float my_score = -INFINITY;
+        for (int t = tid; t < batch_size; t += BLOCK) {
+          float* reduced =
+              var_ws + (long)t * (total_tiles_c + 1) + total_tiles_c;
+          float quad;
+          if (fold) {
+            quad = fold_quad(wp, t);
+            // The owner of candidate t publishes the reduced value.
+            if (t == i) cstore(reduced, quad);
+          } else {
+            quad = cload(reduced);
+          }
+          const float score =
+              score_of(quad, cload(mu_ws + t), cload(dist_ws + t));
+          local_max = fmaxf(local_max, score);
+          if (t == i) my_score = score;
+        }
+        float batch_max = block_reduce(local_max, red, fmax_, -INFINITY);
+        // my_score lives in the thread with tid == i%BLOCK (B <= BLOCK):
+        // broadcast through LDS.
+        if (tid == (i % BLOCK) && i < BLOCK) red[6] = my_score;
+        __syncthreads();
+        const float new_r = red[6];
+        if (tid == 0) {
+          s_scalar = fmaxf(cload(best_reward), batch_max);
+          if (i == 0) cstore(best_reward, s_scalar);
+        }
+        __syncthreads();
+        const float new_best = s_scalar;
+        const int me = batch_start + i;
+        const float old_r = cload(rewards + me);
+        const bool improved = new_r > old_r;
+        const float old_pert = cload(perturbations + me);
+        float pert = improved ? old_pert : old_pert * penalize_factor;
+        float reward = improved ? new_r : old_r;
+        const bool dead = (pert < perturbation_lower_bound) &&
+                          (reward != new_best);
+        if (improved) {
+          for (int j = tid; j < dc; j += BLOCK) {
+            cstore(pool_cont + me * dc + j, out_cont[i * dc + j]);
+          }
+        }
+        if (dead) {
+          for (int j = tid; j < dc; j += BLOCK) {
+            cstore(pool_cont + me * dc + j,
+                   vz_rng_uniform<float>(seed_update, offset ^ 0x5151ull,
+                                  (unsigned)(me * dc + j)));
+          }
+          reward = -INFINITY;
+          pert = base_perturbation;
+        }
+        if (tid == 0) {
+          cstore(rewards + me, reward);
+          cstore(perturbations + me, pert);
+        }
+        __syncthreads();
+      }
+      VZ_SWEEP_PROF(6)
+      grid_sync(barrier_buf, bar_target);
+      VZ_SWEEP_PROF(7)
     }
-    VZ_SWEEP_PROF(6)
-    grid_sync(barrier_buf);
-    VZ_SWEEP_PROF(7)
+  }
+
+  // Resident mode: every owner holds the same final state; workgroup 0
+  // hands it back. With iterations == 0 nothing changed (and no barrier
+  // orders this store after the other workgroups' prologue loads).
+  if (resident && blockIdx.x == 0 && iterations > 0) {
+    for (int e = tid; e < pool_elems; e += BLOCK) {
+      cstore(pool_cont + e, st_pool[e]);
+    }
+    for (int p = tid; p < pool_size; p += BLOCK) {
+      cstore(rewards + p, st_rewards[p]);
+      cstore(perturbations + p, st_perts[p]);
+    }
+    if (tid == 0) cstore(best_reward, st_best);
   }
 
   if (blockIdx.x == 0 && tid == 0) {
@@ -400,7 +687,8 @@ extern "C" int launch_eagle_sweep(
     float* best_reward, unsigned long long* iter_ptr,
     unsigned int* barrier_buf, const float* x, const float* inv_ls,
     const float* alpha, const float* kinv, float* out_cont, float* k_ws,
-    float* mu_ws, float* dist_ws, float* var_ws, int n_batches,
+    float* mu_ws, float* dist_ws, float* var_ws, float* slot_ws,
+    int n_batches,
     int batch_size, int pool_size, int dc, int n, long long it_start,
     long long iterations, float visibility, float gravity,
     float neg_gravity, float norm_scale, float penalize_factor,
@@ -446,7 +734,7 @@ extern "C" int launch_eagle_sweep(
   void* args[] = {
       &pool_cont, &rewards, &perturbations, &best_reward, &iter_ptr,
       &barrier_buf, &x, &inv_ls, &alpha, &kinv, &out_cont, &k_ws,
-      &mu_ws, &dist_ws, &var_ws, &n_batches, &batch_size, &pool_size,
+      &mu_ws, &dist_ws, &var_ws, &slot_ws, &n_batches, &batch_size, &pool_size,
       &dc, &n, &it_start, &iterations, &visibility, &gravity,
       &neg_gravity, &norm_scale, &penalize_factor,
       &perturbation_lower_bound, &base_perturbation, &seed_suggest,

@@ -158,7 +158,8 @@ extern "C" int launch_eagle_sweep(
     float* best_reward, unsigned long long* iter_ptr,
     unsigned int* barrier_buf, const float* x, const float* inv_ls,
     const float* alpha, const float* kinv, float* out_cont, float* k_ws,
-    float* mu_ws, float* dist_ws, float* var_ws, int n_batches,
+    float* mu_ws, float* dist_ws, float* var_ws, float* slot_ws,
+    int n_batches,
     int batch_size, int pool_size, int dc, int n, long long it_start,
     long long iterations, float visibility, float gravity,
     float neg_gravity, float norm_scale, float penalize_factor,
@@ -1467,6 +1468,8 @@ int64_t eagle_sweep(
   inv_ls = check_f32(inv_ls, "inv_ls");
   alpha = check_f32(alpha, "alpha");
   kinv = check_f32(kinv, "kinv");
+  // Word 0 counts barrier arrivals upwards over one launch: the caller
+  // zeroes it before every call. Word 1 is unused.
   TORCH_CHECK(barrier_buf.numel() >= 2, "barrier_buf must be int32 (2,)");
   TORCH_CHECK(x.dim() == 2, "x must be (N, Dc)");
   const int64_t dc64 = x.size(1), n64 = x.size(0);
@@ -1512,6 +1515,13 @@ int64_t eagle_sweep(
   const long tiles_n = (n + 63) / 64;
   TORCH_CHECK(var_ws.numel() >= batch_size * (tiles_n * tiles_n + 1),
               "var_ws must be (B, tiles^2 + 1)");
+  // Two parity slots of (candidates, mu, dist): phase A of iteration `it`
+  // writes slot it & 1 and every owning workgroup reads it back in RC, so
+  // the next iteration's A (which follows RC with no grid barrier) never
+  // overwrites what a slower workgroup still reads. See eagle_sweep.hip.
+  torch::Tensor slot_ws = torch::empty(
+      {2, batch_size * (dc64 + 2)},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
   const int ret = launch_eagle_sweep(
       pool_cont.data_ptr<float>(), rewards.data_ptr<float>(),
       perturbations.data_ptr<float>(), best_reward.data_ptr<float>(),
@@ -1521,7 +1531,7 @@ int64_t eagle_sweep(
       alpha.data_ptr<float>(), kinv.data_ptr<float>(),
       out_cont.data_ptr<float>(), k_ws.data_ptr<float>(),
       mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
-      var_ws.data_ptr<float>(),
+      var_ws.data_ptr<float>(), slot_ws.data_ptr<float>(),
       (int)n_batches, (int)batch_size, (int)pool_size, dc, n,
       (long long)it_start, (long long)iterations, (float)visibility,
       (float)gravity, (float)neg_gravity, (float)norm_scale,

@@ -33,6 +33,21 @@ def make_k(r, n):
 
 ext = ops.require_ext()
 which = sys.argv[1] if len(sys.argv) > 1 else 'all'
+if which == 'impl':
+  # The custom implementations against each other in one process, through
+  # the binding's `impl` argument: interleaved rounds, median and min.
+  impls = sys.argv[2:] or ['v2', 'v6']
+  for r, n in ((2, 1000), (8, 1000), (16, 1000), (3, 2000)):
+    k = make_k(r, n)
+    rounds = {impl: [] for impl in impls}
+    for _ in range(5):
+      for impl in impls:
+        rounds[impl].append(bench(lambda: ext.batched_potrf(k, impl), 10))
+    for impl in impls:
+      ms = sorted(rounds[impl])
+      print(f'R={r:3d} N={n}: {impl:7s} median {ms[2]:7.3f} ms  '
+            f'min {ms[0]:7.3f} ms', flush=True)
+  sys.exit(0)
 for r, n in ((3, 1000), (12, 1000), (3, 2000)):
   k = make_k(r, n)
   if which in ('all', 'custom'):

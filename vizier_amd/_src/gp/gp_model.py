@@ -156,15 +156,18 @@ def cholesky_with_jitter(K: torch.Tensor, amplitude2: torch.Tensor,
 def _use_custom_chol(K: torch.Tensor) -> bool:
   """Opt-in custom batched potrf/trsv on the no-grad GPU path.
 
-  DEFAULT ('both'): the panel-swept v2 potrf (batched_chol.hip —
-  per-matrix panel factor + chip-filling (R x column-tiles) trailing
-  kernels, 2 launches per 32-panel) plus the batched trsv replace
-  MAGMA's ~5000 spotf2 panel launches and the serial rocblas trsv
-  dispatch on the no-grad line-search path. A/B at the headline shape:
-  fit 153.6 -> 150.0 ms, steady suggest 350 -> 340 ms. (The v1
-  one-workgroup-per-matrix factorization measured SLOWER — 16 CUs
-  busy, latency-chained panels — and was replaced by v2.) Opt out with
-  VIZIER_AMD_CUSTOM_CHOL=0 / trsv-only with =trsv.
+  DEFAULT ('both'): the panel-swept potrf (batched_chol.hip, 2 launches
+  per 32-column round: a panel kernel and a trailing update) plus the
+  batched trsv replace MAGMA's ~5000 spotf2 panel launches and the serial
+  rocblas trsv dispatch on the no-grad line-search path. A/B of its first
+  form, v2, at the headline shape: fit 153.6 -> 150.0 ms, steady suggest
+  350 -> 340 ms. The default is now v6: the same rounds and the same
+  bits with the trailing update on 64 x 64 tiles and a
+  column-wise panel solve, 2.8 -> 0.63 ms per (8, 1000, 1000)
+  factorization (profiles/bench_potrf_tiled.md). (The v1
+  one-workgroup-per-matrix factorization measured SLOWER: 16 CUs busy,
+  latency-chained panels.) Opt out with VIZIER_AMD_CUSTOM_CHOL=0 /
+  trsv-only with =trsv.
   """
   mode = os.environ.get('VIZIER_AMD_CUSTOM_CHOL', 'both')
   if mode not in ('1', 'both'):

@@ -804,9 +804,12 @@ extern "C" int launch_batched_potrf_coop(float* A, int* info,
 //     k reads);
 //   - the trailing update is in-place on disjoint (i, j >= jb) tiles.
 // Per-element fma chains are IDENTICAL to v2, so v4 results are
-// bit-identical to v2's. Measured: the A/B that motivated this is the
-// ~44 us launch+L2-flush turnaround BETWEEN dependent kernels (potrf
-// R=3 == R=12 == 2.85 ms on v2 — launch-bound, not work-bound).
+// bit-identical to v2's. What motivated it was potrf R=3 == R=12 ==
+// 2.85 ms on v2, read then as a ~44 us launch + L2-flush turnaround
+// BETWEEN dependent kernels. That reading was wrong: the time is the
+// serial chain inside v2's critical workgroups, which is why halving the
+// launches did not help (113 us per round here) and why v6, with v2's
+// launch count, takes 0.63 ms (see the v6 header).
 
 __device__ __forceinline__ void wave_factor_diag(
     const float* __restrict__ M, int n, int k0, int nb,
@@ -963,13 +966,14 @@ batched_potrf_final_kernel(float* __restrict__ A, int* __restrict__ info,
 //
 // Why a 5th design: the per-kernel cost of v2's 63 launches is NOT
 // launch overhead (a 63-deep chain of trivial kernels runs at 4.4
-// us/launch) and NOT uncoalesced access (LDS staging changed nothing)
-// — it is the end-of-kernel release fence, which writes back and
-// invalidates the per-XCD L2s (~40-65 us when megabytes are dirty;
-// same effect eagle_sweep.hip documents for device-scope fences). The
-// fix must therefore run the whole factorization in ONE kernel while
-// keeping the bulk data CACHED — which a right-looking update cannot
-// do (v3: the trailing matrix is cross-workgroup mutable).
+// us/launch) and NOT uncoalesced access (LDS staging changed nothing).
+// It was put down to an end-of-kernel release fence writing back and
+// invalidating the per-XCD L2s (~40-65 us), and v5 was built to run the
+// whole factorization in ONE kernel with the bulk data CACHED, which a
+// right-looking update cannot do (v3: the trailing matrix is
+// cross-workgroup mutable). The premise does not hold: v6 keeps all 63
+// kernel boundaries and the same dirty bytes and runs in 0.63 ms, so a
+// boundary costs microseconds and v2's time is inside its kernels.
 //
 // Left-looking solves it:
 //   - the INPUT matrix A is never written (output is separate), so
@@ -1215,10 +1219,400 @@ extern "C" int launch_batched_potrf_v5(const float* A, float* panels,
   return 0;
 }
 
-// True iff some round of the v2 factorization of an n x n matrix runs
+// -- v6 (default): v2's rounds with the work split differently -----------
+//
+// Same two launches per round, same parking rule for the diagonal block
+// and, element by element, the same floating-point operations in the same
+// order as v2, so the lower triangle of L is bit-identical
+// (tests/test_potrf_tiled.py). v2's ~40-50 us per kernel was the length of
+// the dependent chain on its critical workgroup, not work and not a fence:
+//   - trailing: v2's strip-0 workgroup walks all the rows below it, one
+//     thread per row, with a 4-KB-strided read-modify-write of M. v6 runs
+//     one workgroup per 64 x 64 tile of the lower triangle, 4 x 4 outputs
+//     per thread from two p-major LDS slices;
+//   - panel: v2's wave factor broadcasts through LDS permutes and its row
+//     solve is a 528-fma dependent chain per row fed by scalar LDS reads.
+//     v6 broadcasts with v_readlane and solves column by column: for p
+//     ascending v[p] = x[p] / d[p][p], then x[j] -= v[p] d[j][p] for all
+//     j > p at once. Every x[j] still sees p ascending, so the bits are
+//     v2's; the chain is 32 x (divide + fma). Rows go global -> registers
+//     -> global, issued before the factor, and a workgroup is one wave of
+//     64 rows: no block barrier. 64 rows beat 256 (one factoring wave,
+//     three waiting) by 4 to 6 % of a factorization at every shape timed
+//     (profiles/bench_potrf_tiled.md).
+
+#define PANEL_ROWS 64  // rows per v6 panel workgroup: one per lane
+#define TT 64          // edge of a trailing tile
+#define TLD (TT + 4)   // p-major LDS row: padded, still 16-byte aligned
+
+// Row `row` of M, columns col0 .. col0 + 31, into registers. Indices are
+// clamped into the matrix instead of predicated, so all the loads issue
+// back to back and nothing waits in between; what a clamp duplicates is
+// never used by the caller. VEC needs n % 4 == 0, col0 % 4 == 0 and a
+// 16-byte aligned M.
+template <bool VEC>
+__device__ __forceinline__ void potrf_load_row(const float* __restrict__ M,
+                                               int n, int row, int col0,
+                                               float out[NB]) {
+  const float* p = M + (long)min(row, n - 1) * n;
+  if (VEC) {
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+      const float4 v =
+          *reinterpret_cast<const float4*>(p + min(col0 + 4 * q, n - 4));
+      out[4 * q] = v.x;
+      out[4 * q + 1] = v.y;
+      out[4 * q + 2] = v.z;
+      out[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) out[c] = p[min(col0 + c, n - 1)];
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void potrf_store_row(float* __restrict__ p,
+                                                int ncols,
+                                                const float v[NB]) {
+  if (VEC) {
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+      if (4 * q < ncols) {
+        *reinterpret_cast<float4*>(p + 4 * q) =
+            make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      if (c < ncols) p[c] = v[c];
+    }
+  }
+}
+
+__device__ __forceinline__ float potrf_readlane(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// v2's row solve `xv -= v[p] * diag[j][p]` is not one fma throughout. As
+// hipcc compiles it, the vectorizer pairs the multiplies of the last
+// min(10, j rounded down to even) steps of column j into packed multiplies,
+// whose products are rounded before the subtraction; the earlier steps
+// contract to fma (read off the optimized IR and the ISA: 130 v_pk_mul_f32
+// and 260 v_sub_f32 next to 268 fused steps). L depends on that split, so
+// v6 spells it out, and tests/test_potrf_tiled.py fails if a compiler
+// splits v2 differently.
+__host__ __device__ constexpr bool potrf_solve_rounds_product(int j, int p) {
+  return p >= j - ((j & ~1) < 10 ? (j & ~1) : 10);
+}
+
+__device__ __forceinline__ float potrf_sub_rounded_product(float x, float a,
+                                                           float b) {
+#pragma clang fp contract(off)
+  const float prod = a * b;
+  return x - prod;
+}
+
+// Grid (R, row tiles of 64), one wave. As in v2 every workgroup
+// factors the diagonal block itself and workgroup y == 0 writes it out: in
+// place when it is the matrix's only workgroup, else parked in `dscratch`.
+// A partial last block (nb < 32, no rows below it) is padded with the
+// identity: the padding's pivots are 1 and its multipliers 0, so the
+// nb x nb corner sees exactly the operations of a factor of width nb and
+// the wave factor needs no `c < nb` predicates.
+template <bool VEC>
+__global__ __launch_bounds__(PANEL_ROWS) void
+batched_potrf_panel_cols_kernel(float* __restrict__ A,
+                                int* __restrict__ info,
+                                float* __restrict__ dscratch, int n,
+                                int k0) {
+  // dcol[p][j] = d[j][p]: what column step p of the solve reads is
+  // contiguous, and a b128 read of it is one broadcast.
+  __shared__ __attribute__((aligned(16))) float dcol[NB][NB];
+  const int r = blockIdx.x;
+  float* M = A + (long)r * n * n;
+  static_assert(PANEL_ROWS == WAVE_SIZE, "one wave factors and solves");
+  const int lane = threadIdx.x;
+  const int nb = min(NB, n - k0);
+  const int i = k0 + NB + (int)blockIdx.y * PANEL_ROWS + lane;
+
+  float x[NB], row[NB];
+  potrf_load_row<VEC>(M, n, i, k0, x);
+  potrf_load_row<VEC>(M, n, k0 + lane, k0, row);
+#pragma unroll
+  for (int c = 0; c < NB; ++c) {
+    if (lane >= nb || c >= nb) row[c] = (c == lane) ? 1.0f : 0.0f;
+  }
+  // Lane l < 32 holds row l of the block. Entries above the diagonal
+  // carry values nobody reads (v2 masks them off instead): only d[j][p]
+  // with p <= j is ever used or stored.
+  int fc = 0;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const float piv = potrf_readlane(row[j], j);
+    const bool ok = piv > 0.0f;
+    const float d = ok ? sqrtf(piv) : 1.0f;
+    if (!ok && fc == 0) fc = k0 + j + 1;
+    row[j] = (lane == j) ? d : row[j] / d;
+#pragma unroll
+    for (int c = j + 1; c < NB; ++c) {
+      const float lcj = potrf_readlane(row[j], c);
+      row[c] = fmaf(-row[j], lcj, row[c]);
+    }
+  }
+  if (lane < NB) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) dcol[c][lane] = row[c];
+  }
+  __syncthreads();
+  if (blockIdx.y == 0 && lane < nb) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      if (c > lane) row[c] = 0.0f;
+    }
+    float* dst = dscratch != nullptr
+        ? dscratch + (long)r * NB * NB + lane * NB
+        : M + (long)(k0 + lane) * n + k0;
+    potrf_store_row<VEC>(dst, nb, row);
+    if (lane == 0 && fc != 0 && info[r] == 0) info[r] = fc;
+  }
+  if (k0 + NB >= n) return;  // uniform: no rows below this block
+
+  // Lanes past the last row solve a clamped copy and store nothing.
+#pragma unroll
+  for (int p = 0; p < NB; ++p) {
+    float dc[NB];
+#pragma unroll
+    for (int q = p / 4; q < NB / 4; ++q) {
+      const float4 v = *reinterpret_cast<const float4*>(&dcol[p][4 * q]);
+      dc[4 * q] = v.x;
+      dc[4 * q + 1] = v.y;
+      dc[4 * q + 2] = v.z;
+      dc[4 * q + 3] = v.w;
+    }
+    const float v = x[p] / dc[p];
+    x[p] = v;
+#pragma unroll
+    for (int j = p + 1; j < NB; ++j) {
+      x[j] = potrf_solve_rounds_product(j, p)
+          ? potrf_sub_rounded_product(x[j], v, dc[j])
+          : fmaf(-v, dc[j], x[j]);
+    }
+  }
+  if (i < n) potrf_store_row<VEC>(M + (long)i * n + k0, NB, x);
+}
+
+// Grid (R x lower-triangular tile pairs ti >= tj of the trailing matrix),
+// flattened so that R is not bound by gridDim.y; 256 threads, thread
+// (ty, tx) owns the 4 x 4 outputs at rows ib + 4 ty, columns jb + 4 tx.
+// Only full panels have a trailing matrix, so nb == 32 here. Per element
+// acc = 0; acc = fmaf(L[i][k0 + p], L[j][k0 + p], acc), p ascending;
+// M[i][j] -= acc, as in v2. The pair's first workgroup copies the parked
+// diagonal block into place (rows k0 .. k0 + 31: read by nobody here).
+template <bool VEC>
+__global__ __launch_bounds__(CB) void
+batched_potrf_trailing_tiled_kernel(float* __restrict__ A,
+                                    const float* __restrict__ dscratch,
+                                    int n, int k0, int pairs) {
+  __shared__ __attribute__((aligned(16))) float As[NB][TLD];
+  __shared__ __attribute__((aligned(16))) float Bs[NB][TLD];
+  const int r = blockIdx.x / pairs;
+  const int pair = blockIdx.x % pairs;
+  float* M = A + (long)r * n * n;
+  const int tid = threadIdx.x;
+
+  if (dscratch != nullptr && pair == 0) {
+    const float* ds = dscratch + (long)r * NB * NB;
+    if (VEC) {
+      const int di = tid / (NB / 4), dq = tid % (NB / 4);
+      *reinterpret_cast<float4*>(M + (long)(k0 + di) * n + k0 + 4 * dq) =
+          *reinterpret_cast<const float4*>(ds + di * NB + 4 * dq);
+    } else {
+      for (int e = tid; e < NB * NB; e += CB) {
+        M[(long)(k0 + e / NB) * n + k0 + e % NB] = ds[e];
+      }
+    }
+  }
+
+  // pair = ti (ti + 1) / 2 + tj with tj <= ti.
+  int ti = (int)((sqrtf(8.0f * pair + 1.0f) - 1.0f) * 0.5f);
+  while (ti * (ti + 1) / 2 > pair) --ti;
+  while ((ti + 1) * (ti + 2) / 2 <= pair) ++ti;
+  const int tj = pair - ti * (ti + 1) / 2;
+  const int ib = k0 + NB + ti * TT;
+  const int jb = k0 + NB + tj * TT;
+  const int ty = tid / 16, tx = tid % 16;
+  const int i0 = ib + 4 * ty, j0 = jb + 4 * tx;
+
+  // All global loads first: the two 64 x 32 operand slices, then C.
+  // Rows and columns past n are clamped; their products are not stored.
+  float c[4][4];
+  if (VEC) {
+    float4 a4[2], b4[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int e = tid + s * CB;
+      const int rr = e / 8, cq = e % 8;
+      a4[s] = *reinterpret_cast<const float4*>(
+          M + (long)min(ib + rr, n - 1) * n + k0 + 4 * cq);
+      b4[s] = *reinterpret_cast<const float4*>(
+          M + (long)min(jb + rr, n - 1) * n + k0 + 4 * cq);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const float4 v = *reinterpret_cast<const float4*>(
+          M + (long)min(i0 + a, n - 1) * n + min(j0, n - 4));
+      c[a][0] = v.x;
+      c[a][1] = v.y;
+      c[a][2] = v.z;
+      c[a][3] = v.w;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int e = tid + s * CB;
+      const int rr = e / 8, cq = e % 8;
+      As[4 * cq][rr] = a4[s].x;
+      As[4 * cq + 1][rr] = a4[s].y;
+      As[4 * cq + 2][rr] = a4[s].z;
+      As[4 * cq + 3][rr] = a4[s].w;
+      Bs[4 * cq][rr] = b4[s].x;
+      Bs[4 * cq + 1][rr] = b4[s].y;
+      Bs[4 * cq + 2][rr] = b4[s].z;
+      Bs[4 * cq + 3][rr] = b4[s].w;
+    }
+  } else {
+    float a1[8], b1[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int e = tid + s * CB;
+      const int rr = e / NB, cc = e % NB;
+      a1[s] = M[(long)min(ib + rr, n - 1) * n + k0 + cc];
+      b1[s] = M[(long)min(jb + rr, n - 1) * n + k0 + cc];
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        c[a][b] = M[(long)min(i0 + a, n - 1) * n + min(j0 + b, n - 1)];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int e = tid + s * CB;
+      As[e % NB][e / NB] = a1[s];
+      Bs[e % NB][e / NB] = b1[s];
+    }
+  }
+  __syncthreads();
+
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0f;
+  }
+#pragma unroll 8
+  for (int p = 0; p < NB; ++p) {
+    const float4 av = *reinterpret_cast<const float4*>(&As[p][4 * ty]);
+    const float4 bv = *reinterpret_cast<const float4*>(&Bs[p][4 * tx]);
+    const float al[4] = {av.x, av.y, av.z, av.w};
+    const float bl[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        acc[a][b] = fmaf(al[a], bl[b], acc[a][b]);
+      }
+    }
+  }
+
+  // Lower triangle only; whole float4 where the four columns are in it.
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = i0 + a;
+    if (i >= n) break;
+    float* dst = M + (long)i * n + j0;
+    if (VEC && j0 + 3 <= i) {
+      *reinterpret_cast<float4*>(dst) =
+          make_float4(c[a][0] - acc[a][0], c[a][1] - acc[a][1],
+                      c[a][2] - acc[a][2], c[a][3] - acc[a][3]);
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (j0 + b <= i) dst[b] = c[a][b] - acc[a][b];
+      }
+    }
+  }
+}
+
+// What one round launches: the panel's row tiles and the trailing
+// update's workgroups per matrix (v2: 64-column strips; v6: tile pairs).
+struct PotrfRound {
+  int panel_tiles;
+  int trailing_wgs;
+};
+
+// Rows per panel workgroup of the v2 (impl != 6) and v6 launchers.
+extern "C" int batched_potrf_panel_rows(int impl) {
+  return impl == 6 ? PANEL_ROWS : CB;
+}
+
+static PotrfRound potrf_round(int n, int k0, int impl) {
+  const int panel_rows = batched_potrf_panel_rows(impl);
+  const int nb = (n - k0) < NB ? (n - k0) : NB;
+  const int rows = n - (k0 + nb);
+  PotrfRound s;
+  s.panel_tiles = rows > 0 ? (rows + panel_rows - 1) / panel_rows : 1;
+  const int t = (rows + TT - 1) / TT;
+  s.trailing_wgs = impl == 6 ? t * (t + 1) / 2 : t;
+  return s;
+}
+
+// True iff some round of the v2 / v6 factorization of an n x n matrix runs
 // more than one row tile, i.e. needs the (R, NB, NB) diagonal scratch.
-extern "C" int batched_potrf_needs_scratch(int n) {
-  return n - NB > CB ? 1 : 0;
+extern "C" int batched_potrf_needs_scratch(int n, int impl) {
+  return n - NB > batched_potrf_panel_rows(impl) ? 1 : 0;
+}
+
+// Round 0, the largest, as the launchers below run it: {panel row tiles,
+// trailing workgroups per matrix}.
+extern "C" void batched_potrf_launch_shape(int n, int impl, int out[2]) {
+  const PotrfRound s = potrf_round(n, 0, impl);
+  out[0] = s.panel_tiles;
+  out[1] = s.trailing_wgs;
+}
+
+extern "C" void launch_batched_potrf_v6(float* A, int* info,
+                                        float* dscratch, int r, int n,
+                                        hipStream_t stream) {
+  const bool vec = n % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0;
+  for (int k0 = 0; k0 < n; k0 += NB) {
+    const PotrfRound s = potrf_round(n, k0, 6);
+    // More than one row tile implies rows below the block, so the
+    // trailing launch that moves the parked block into place follows.
+    float* park = s.panel_tiles > 1 ? dscratch : nullptr;
+    if (vec) {
+      hipLaunchKernelGGL(batched_potrf_panel_cols_kernel<true>,
+                         dim3(r, s.panel_tiles), dim3(PANEL_ROWS), 0,
+                         stream, A, info, park, n, k0);
+    } else {
+      hipLaunchKernelGGL(batched_potrf_panel_cols_kernel<false>,
+                         dim3(r, s.panel_tiles), dim3(PANEL_ROWS), 0,
+                         stream, A, info, park, n, k0);
+    }
+    if (s.trailing_wgs > 0) {
+      if (vec) {
+        hipLaunchKernelGGL(batched_potrf_trailing_tiled_kernel<true>,
+                           dim3(r * s.trailing_wgs), dim3(CB), 0, stream,
+                           A, (const float*)park, n, k0, s.trailing_wgs);
+      } else {
+        hipLaunchKernelGGL(batched_potrf_trailing_tiled_kernel<false>,
+                           dim3(r * s.trailing_wgs), dim3(CB), 0, stream,
+                           A, (const float*)park, n, k0, s.trailing_wgs);
+      }
+    }
+  }
 }
 
 extern "C" void launch_batched_potrf_v2(float* A, int* info,
@@ -1242,18 +1636,18 @@ extern "C" void launch_batched_potrf_v2(float* A, int* info,
   }
 }
 
+// impl: 6 = v6, 4 = v4, else v2. v4 measured SLOWER than v2 at the headline shape (3.63
+// vs 2.85 ms, R=3 N=1000): the fused kernel's three inlined 32-wide solves
+// blow its register budget (VGPR 256 + 248 AGPRs, occupancy 1 wave/SIMD
+// vs v2's 4). Kept for experiments.
 extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
-                                     int r, int n, hipStream_t stream) {
-  // v4 measured SLOWER than v2 at the headline shape (3.63 vs 2.85 ms,
-  // R=3 N=1000): the fused kernel's three inlined 32-wide solves blow
-  // its register budget (VGPR 256 + 248 AGPRs, occupancy 1 wave/SIMD
-  // vs v2's 4). Opt-in via VIZIER_AMD_CHOL_IMPL=v4 for experiments.
-  static int use_v4 = -1;
-  if (use_v4 < 0) {
-    const char* env = std::getenv("VIZIER_AMD_CHOL_IMPL");
-    use_v4 = (env != nullptr && env[0] == 'v' && env[1] == '4') ? 1 : 0;
+                                     int r, int n, int impl,
+                                     hipStream_t stream) {
+  if (impl == 6) {
+    launch_batched_potrf_v6(A, info, dscratch, r, n, stream);
+    return;
   }
-  if (!use_v4) {
+  if (impl != 4) {
     launch_batched_potrf_v2(A, info, dscratch, r, n, stream);
     return;
   }

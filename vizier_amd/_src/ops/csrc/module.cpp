@@ -130,9 +130,12 @@ extern "C" void launch_setpe_logdet(
     float* out, int b, int q, float jitter, float threshold,
     float explore_coef, float penalty_coef, float tr_radius,
     hipStream_t stream);
-extern "C" int batched_potrf_needs_scratch(int n);
+extern "C" int batched_potrf_panel_rows(int impl);
+extern "C" int batched_potrf_needs_scratch(int n, int impl);
+extern "C" void batched_potrf_launch_shape(int n, int impl, int out[2]);
 extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
-                                     int r, int n, hipStream_t stream);
+                                     int r, int n, int impl,
+                                     hipStream_t stream);
 extern "C" int launch_batched_potrf_coop(float* A, int* info,
                                          unsigned int* bar, int r, int n,
                                          hipStream_t stream);
@@ -1136,7 +1139,65 @@ torch::Tensor hv_scalarize_tr(
   return out;
 }
 
-std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
+// Implementation ladder. `impl` is "v2" .. "v6"; "" means
+// VIZIER_AMD_CHOL_IMPL, read once per process, and v6 when that is unset.
+// v2 and v6 factor the same bits (tests/test_potrf_tiled.py). Timings at
+// N = 1000:
+//   v6 (default): v2's two launches per 32-column round, trailing update
+//       on 64 x 64 tiles and a column-wise panel solve: 0.53 / 0.63 /
+//       0.71 ms at R = 2 / 8 / 16 (profiles/bench_potrf_tiled.md).
+//   v2: 2.8 ms whatever R. A 63-deep chain of trivial kernels runs at
+//       4.4 us per launch and LDS-staged coalescing changed nothing, so
+//       the ~45 us per kernel were taken for an end-of-kernel fence. They
+//       are the serial chain inside the critical workgroup: one strip's
+//       workgroup walks every row below it, and each panel row is a
+//       528-step dependent chain. v6 runs the same rounds with the same
+//       kernel boundaries in under a quarter of the time.
+//   v5: persistent left-looking cooperative kernel (read-only input
+//       stays cached, panel-major once-written output, diagonal via
+//       agent-scope scratch), 3.15 ms: ~500 barrier-separated LDS staging
+//       steps at occupancy 2.
+//   v3: right-looking cooperative, 2x slower than v2 (the trailing matrix
+//       is cross-workgroup mutable, so all its traffic is memory-side).
+//   v4: fused one-kernel-per-round with recompute, occupancy 1
+//       (VGPR 256 + 248 AGPRs), 3.63 ms.
+int resolve_potrf_impl(const std::string& impl) {
+  const auto parse = [](const std::string& s) {
+    return s.size() == 2 && s[0] == 'v' && s[1] >= '2' && s[1] <= '6'
+        ? s[1] - '0' : 0;
+  };
+  if (!impl.empty()) {
+    const int version = parse(impl);
+    TORCH_CHECK(version != 0, "batched_potrf impl must be one of v2, v3, "
+                "v4, v5, v6, got '", impl, "'");
+    return version;
+  }
+  static const int from_env = [&]() {
+    const char* env = std::getenv("VIZIER_AMD_CHOL_IMPL");
+    const int version = parse(env == nullptr ? "" : env);
+    return version != 0 ? version : 6;
+  }();
+  return from_env;
+}
+
+// What the v2 / v6 launcher runs for an n x n matrix: (rows per panel
+// workgroup, panel row tiles of round 0, trailing workgroups per matrix
+// of round 0, 1 if it parks diagonal blocks in a scratch tensor else 0).
+// Round 0 is the largest round. Pure host arithmetic.
+std::vector<int64_t> batched_potrf_launch_shape_py(int64_t n,
+                                                   const std::string& impl) {
+  const int version = resolve_potrf_impl(impl);
+  TORCH_CHECK(version == 2 || version == 6,
+              "launch shape is defined for v2 and v6 only");
+  TORCH_CHECK(n >= 1, "n must be >= 1");
+  int out[2];
+  batched_potrf_launch_shape((int)n, version, out);
+  return {batched_potrf_panel_rows(version), out[0], out[1],
+          batched_potrf_needs_scratch((int)n, version)};
+}
+
+std::vector<torch::Tensor> batched_potrf(torch::Tensor K,
+                                         const std::string& impl_name) {
   // (R, N, N) -> (L in a fresh tensor, info (R,) int32). Only the LOWER
   // triangle of L is defined: the default path leaves K's values in the
   // strict upper triangle outside the 32x32 diagonal blocks, and
@@ -1149,30 +1210,8 @@ std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
               "batched_potrf needs R >= 1 and N >= 1, got R = ",
               K.size(0), ", N = ", K.size(1));
   const int r = K.size(0), n = K.size(1);
+  const int impl = resolve_potrf_impl(impl_name);
   auto info = torch::zeros({r}, K.options().dtype(torch::kInt32));
-  // Implementation ladder (VIZIER_AMD_CHOL_IMPL=v2|v3|v4|v5, default
-  // v2 — every alternative was A/B'd SLOWER at the headline shape):
-  //   v2 (default): 2 launches per 32-panel round; 2.85 ms at
-  //       (R=3..12, N=1000). Execution-bound: a 63-deep trivial-kernel
-  //       chain runs at 4.4 us/launch, LDS-staged coalescing changed
-  //       nothing, so the per-kernel ~45 us is genuine work+fence.
-  //   v5: persistent left-looking cooperative kernel (read-only input
-  //       stays cached, panel-major once-written output, diagonal via
-  //       agent-scope scratch) — 3.15 ms: the per-panel LDS staging
-  //       loop (~500 sync'd iterations) and occupancy 2 eat the
-  //       saved inter-kernel fences.
-  //   v3: right-looking cooperative — 2x slower (trailing matrix is
-  //       cross-workgroup mutable -> all traffic memory-side).
-  //   v4: fused one-kernel-per-round with recompute — occupancy 1
-  //       (VGPR 256 + 248 AGPRs).
-  static const int impl = []() {
-    const char* env = std::getenv("VIZIER_AMD_CHOL_IMPL");
-    if (env == nullptr) return 2;
-    const std::string s(env);
-    if (s == "v5") return 5;
-    if (s == "v3") return 3;
-    return 2;  // v2/v4 re-checked downstream
-  }();
   if (impl == 5) {
     auto L = torch::empty_like(K);
     const long pk = (n + 31) / 32;
@@ -1198,16 +1237,18 @@ std::vector<torch::Tensor> batched_potrf(torch::Tensor K) {
       return {L, info};
     }
   }
+  // v3 / v5 fall back to v2 when their cooperative launch is refused.
+  const int launcher = impl == 6 || impl == 4 ? impl : 2;
   // Rounds with more than one row tile park their factored diagonal
   // block here instead of overwriting what the other tiles still read.
   torch::Tensor dscratch;
   float* dscratch_p = nullptr;
-  if (batched_potrf_needs_scratch(n)) {
+  if (batched_potrf_needs_scratch(n, launcher)) {
     dscratch = torch::empty({r, 32, 32}, K.options());
     dscratch_p = dscratch.data_ptr<float>();
   }
   launch_batched_potrf(L.data_ptr<float>(), info.data_ptr<int>(),
-                       dscratch_p, r, n, current_stream());
+                       dscratch_p, r, n, launcher, current_stream());
   return {L, info};
 }
 
@@ -1669,7 +1710,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Batched Cholesky K (R, N, N) fp32 -> (L, info). Only the lower "
         "triangle of L is defined; the strict upper triangle holds "
         "unspecified values. info[r] is the 1-based first column whose "
-        "pivot is not > 0 (zero, negative or NaN), 0 on success (gfx950)");
+        "pivot is not > 0 (zero, negative or NaN), 0 on success. impl = "
+        "v2 .. v6; '' = VIZIER_AMD_CHOL_IMPL, else v6 (gfx950)",
+        py::arg("K"), py::arg("impl") = "");
+  m.def("batched_potrf_launch_shape", &batched_potrf_launch_shape_py,
+        "(rows per panel workgroup, panel row tiles of round 0, trailing "
+        "workgroups per matrix of round 0, uses scratch) of the v2 / v6 "
+        "launcher for an n x n matrix; host arithmetic only",
+        py::arg("n"), py::arg("impl") = "");
   m.def("batched_trsv_lower", &batched_trsv_lower,
         "Batched forward substitution L z = b (gfx950). variant 0 = "
         "pipelined register-resident solve, 1 = LDS-staged solve; "

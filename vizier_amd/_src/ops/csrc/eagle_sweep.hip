@@ -76,7 +76,10 @@
 //
 // Determinism: phases replicate the standalone kernels VERBATIM (same
 // counter-based RNG streams, same 64x64 tile quadform and partial
-// order, same block-reduce orders), so for N < 4096 the sweep is
+// order, same block-reduce orders; where a loop is restructured to keep
+// its loads in flight, vz_quadform_tile_pipelined and sweep_kvec below,
+// every value still comes from the same operations on the same operands
+// in the same order), so for N < 4096 the sweep is
 // BIT-IDENTICAL to the step kernels of the hipGraph path for the same
 // seeds: the whole pool state, asserted by tests/test_sweep_kernel.py
 // and tests/test_gpu_ops.py. For 4096 <= N <= 8192 the standalone
@@ -232,6 +235,195 @@ __device__ __forceinline__ float fold_quad(const float* wp, int q) {
          (wp[VZ_QF_QMAX + q] + wp[3 * VZ_QF_QMAX + q]);
 }
 
+// The sweep's own form of vz_quadform_tile (common.h): every partial is
+// produced by the same operations on the same operands in the same order,
+// so the two stay bit-identical; only when the loads are issued differs.
+// The kernel runs one wave per SIMD, so no other wave hides a wait, and
+// the shared routine's staging loop exposes one memory-side round trip per
+// load (the guarded ternary around the relaxed atomic load keeps the
+// compiler from batching them): 16 dependent round trips per tile. Here a
+// thread puts its 16 loads of k_i / k_j in flight before the first wait.
+// Elements outside the batch or the tile re-read a clamped address and
+// are replaced by the zero the shared routine stores; a branch around the
+// load would bring the waits back.
+template <typename LoadK, typename StoreP>
+__device__ __forceinline__ void vz_quadform_tile_pipelined(
+    const float* __restrict__ kinv, int b, int n, int tile, int tiles_n,
+    float* k_i_lds, float* k_j_lds, LoadK loadk, StoreP store,
+    unsigned long long* prof = nullptr) {
+  constexpr int kStage = VZ_QF_QMAX * VZ_QF_TILE / BLOCK;  // 8 per thread
+  const int tid = threadIdx.x;
+  const bool profme = (prof != nullptr && tid == 0);
+  unsigned long long tq0 = profme ? wall_clock64() : 0;
+  const int ti = tile / tiles_n, tj = tile % tiles_n;
+  const int i0 = ti * VZ_QF_TILE, j0 = tj * VZ_QF_TILE;
+  const int ilen = min(VZ_QF_TILE, n - i0);
+  const int jlen = min(VZ_QF_TILE, n - j0);
+  {
+    // e = tid + u * BLOCK: the column c is the same for every u.
+    const int c = tid % VZ_QF_TILE;
+    const int q0 = tid / VZ_QF_TILE;
+    const int ci = i0 + min(c, ilen - 1), cj = j0 + min(c, jlen - 1);
+    float ri[kStage], rj[kStage];
+#pragma unroll
+    for (int u = 0; u < kStage; ++u) {
+      const long base =
+          (long)min(q0 + u * (BLOCK / VZ_QF_TILE), b - 1) * n;
+      ri[u] = loadk(base + ci);
+      rj[u] = loadk(base + cj);
+    }
+#pragma unroll
+    for (int u = 0; u < kStage; ++u) {
+      const bool inq = q0 + u * (BLOCK / VZ_QF_TILE) < b;
+      k_i_lds[tid + u * BLOCK] = (inq && c < ilen) ? ri[u] : 0.0f;
+      k_j_lds[tid + u * BLOCK] = (inq && c < jlen) ? rj[u] : 0.0f;
+    }
+  }
+  __syncthreads();
+  if (profme) {
+    const unsigned long long tq1 = wall_clock64();
+    prof[0] += tq1 - tq0;
+    tq0 = tq1;
+  }
+  const int wave = tid / WAVE_SIZE;
+  const int lane = tid % WAVE_SIZE;
+  float acc[8];
+#pragma unroll
+  for (int qq = 0; qq < 8; ++qq) acc[qq] = 0.0f;
+  if (lane < jlen) {
+    if (ilen == VZ_QF_TILE) {
+      for (int ib = 0; ib < VZ_QF_TILE; ib += 8) {
+        float kvv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          kvv[u] = kinv[(long)(i0 + ib + u) * n + j0 + lane];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+#pragma unroll
+          for (int qq = 0; qq < 8; ++qq) {
+            acc[qq] = fmaf(
+                k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + ib + u],
+                kvv[u], acc[qq]);
+          }
+        }
+      }
+    } else {
+      for (int i = 0; i < ilen; ++i) {
+        const float kv = kinv[(long)(i0 + i) * n + j0 + lane];
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) {
+          acc[qq] = fmaf(k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + i], kv,
+                         acc[qq]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int qq = 0; qq < 8; ++qq) {
+    const int q = wave * 8 + qq;
+    float v = acc[qq] * k_j_lds[q * VZ_QF_TILE + lane];
+    v = wave_reduce_sum(v);
+    if (lane == 0 && q < b) store(q, v);
+  }
+  __syncthreads();
+  if (profme) prof[1] += wall_clock64() - tq0;
+}
+
+// matern52_of_d2 (common.h) with the roundings it has in the rolled
+// k-vector loop of the step path: 1 + sr is rounded, then one fma adds
+// sr^2 / 3. Inlined into the unrolled four-row loop below, the shared
+// function also gets 1 + sqrt(5) r fused into an fma, which changes the
+// last bit of the k-vector; spelled out here so that it cannot.
+__device__ __forceinline__ float sweep_matern52(float d2) {
+#pragma clang fp contract(off)
+  const float r = sqrtf(fmaxf(d2, 0.0f));
+  const float sr = 2.2360679774997896f * r;  // sqrt(5) * r
+  const float one_sr = 1.0f + sr;
+  return fmaf(sr * sr, 1.0f / 3.0f, one_sr) * __expf(-sr);
+}
+
+// Phase A's k-vector, mu and trust-region distance of one candidate: the
+// loop of the step path (row = tid, tid + BLOCK, ...; j = 0 .. dc - 1 per
+// row; mu_acc and min_linf over the thread's rows in that order), with the
+// loads of up to KV_ROWS rows and KV_CHUNK dimensions in flight together.
+// The rolled form did one load of x, one of xq and one of inv_ls per
+// dimension and waited for all three: rows x dc serialized round trips
+// per thread; this one exposes dc / KV_CHUNK per KV_ROWS rows. (Loading
+// the next chunk while this one is used did not survive the compiler,
+// which moves the load back to the head of the trip.) VEC4 reads x
+// as float4 (dc a multiple of 4, x 16-byte aligned; chosen once per
+// launch); otherwise each element is loaded on its own. Rows past n and
+// dimensions past dc re-read a clamped address and are discarded.
+#define KV_ROWS 4
+#define KV_CHUNK 4
+
+template <bool VEC4>
+__device__ __forceinline__ void sweep_kvec(
+    const float* __restrict__ x, const float* __restrict__ inv_ls,
+    const float* __restrict__ alpha, const float* xq_lds, float* k_row,
+    int dc, int n, float amp2, float& mu_acc, float& min_linf) {
+  for (int row0 = threadIdx.x; row0 < n; row0 += KV_ROWS * BLOCK) {
+    const float* xr[KV_ROWS];
+    float al[KV_ROWS];
+#pragma unroll
+    for (int s = 0; s < KV_ROWS; ++s) {
+      const int rc = min(row0 + s * BLOCK, n - 1);
+      xr[s] = x + (long)rc * dc;
+      al[s] = alpha[rc];
+    }
+    auto load_chunk = [&](float (&buf)[KV_ROWS][KV_CHUNK], int j0) {
+#pragma unroll
+      for (int s = 0; s < KV_ROWS; ++s) {
+        if (VEC4) {
+          const float4 v = *reinterpret_cast<const float4*>(xr[s] + j0);
+          buf[s][0] = v.x; buf[s][1] = v.y; buf[s][2] = v.z; buf[s][3] = v.w;
+        } else {
+#pragma unroll
+          for (int c = 0; c < KV_CHUNK; ++c) {
+            buf[s][c] = xr[s][min(j0 + c, dc - 1)];
+          }
+        }
+      }
+    };
+    float d2[KV_ROWS], linf[KV_ROWS];
+#pragma unroll
+    for (int s = 0; s < KV_ROWS; ++s) d2[s] = linf[s] = 0.0f;
+    for (int j0 = 0; j0 < dc; j0 += KV_CHUNK) {
+      float cur[KV_ROWS][KV_CHUNK];
+      load_chunk(cur, j0);
+      float xq[KV_CHUNK], il[KV_CHUNK];
+#pragma unroll
+      for (int c = 0; c < KV_CHUNK; ++c) {
+        const int jc = VEC4 ? j0 + c : min(j0 + c, dc - 1);
+        xq[c] = xq_lds[jc];
+        il[c] = inv_ls[jc];
+      }
+#pragma unroll
+      for (int c = 0; c < KV_CHUNK; ++c) {
+        if (VEC4 || j0 + c < dc) {
+#pragma unroll
+          for (int s = 0; s < KV_ROWS; ++s) {
+            const float diff = xq[c] - cur[s][c];
+            const float z = diff * il[c];
+            d2[s] = fmaf(z, z, d2[s]);
+            linf[s] = fmaxf(linf[s], fabsf(diff));  // continuous-only
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < KV_ROWS; ++s) {
+      const int row = row0 + s * BLOCK;
+      const bool live = row < n;
+      const float kv = amp2 * sweep_matern52(d2[s]);
+      if (live) cstore(k_row + row, kv);
+      mu_acc = live ? fmaf(kv, al[s], mu_acc) : mu_acc;
+      min_linf = live ? fminf(min_linf, linf[s]) : min_linf;
+    }
+  }
+}
+
 extern "C" __global__ __launch_bounds__(BLOCK) void
 eagle_sweep_kernel(
     float* __restrict__ pool_cont,         // (P, Dc)   [coherent]
@@ -261,7 +453,7 @@ eagle_sweep_kernel(
   __shared__ float scale[MAX_POOL];
   __shared__ float red[8];
   __shared__ float s_scalar;
-  __shared__ float xq_lds[512];
+  __shared__ __attribute__((aligned(16))) float xq_lds[512];
   __shared__ float pool_lds[POOL_LDS_CAP];
   // Resident mode: this workgroup's private copy of the Eagle state.
   __shared__ float st_rewards[MAX_POOL];
@@ -276,6 +468,9 @@ eagle_sweep_kernel(
   const bool stage_pool = !resident && pool_elems <= POOL_LDS_CAP;
   const bool pool_in_lds = resident || stage_pool;
   const bool owner = blockIdx.x < batch_size;
+  // Form of the k-vector loop (sweep_kvec), picked once per launch.
+  const bool x_vec4 = dc % KV_CHUNK == 0 &&
+                      (reinterpret_cast<unsigned long long>(x) & 15) == 0;
   float* st_pool = pool_lds + RESIDENT_CAP;
   const float* pl = resident ? st_pool : pool_lds;
   auto fsum = [](float a, float c) { return a + c; };
@@ -410,19 +605,12 @@ eagle_sweep_kernel(
       // k-vector + mu + trust-region distance for candidate b.
       float mu_acc = 0.0f;
       float min_linf = INFINITY;
-      for (int row = tid; row < n; row += BLOCK) {
-        const float* xr = x + (long)row * dc;
-        float d2 = 0.0f, linf = 0.0f;
-        for (int j = 0; j < dc; ++j) {
-          const float diff = xq_lds[j] - xr[j];
-          const float z = diff * inv_ls[j];
-          d2 = fmaf(z, z, d2);
-          linf = fmaxf(linf, fabsf(diff));  // continuous-only
-        }
-        const float kv = amp2 * matern52_of_d2(d2);
-        cstore(k_ws + (long)b * n + row, kv);
-        mu_acc = fmaf(kv, alpha[row], mu_acc);
-        min_linf = fminf(min_linf, linf);
+      if (x_vec4) {
+        sweep_kvec<true>(x, inv_ls, alpha, xq_lds, k_ws + (long)b * n, dc,
+                         n, amp2, mu_acc, min_linf);
+      } else {
+        sweep_kvec<false>(x, inv_ls, alpha, xq_lds, k_ws + (long)b * n, dc,
+                          n, amp2, mu_acc, min_linf);
       }
       float mu = block_reduce(mu_acc, red, fsum, 0.0f);
       if (tid == 0) {
@@ -454,7 +642,7 @@ eagle_sweep_kernel(
       float* k_j_lds = pool_lds + VZ_QF_QMAX * VZ_QF_TILE;
       for (int tile = blockIdx.x; tile < total_tiles; tile += G) {
         const int t = tile;
-        vz_quadform_tile(
+        vz_quadform_tile_pipelined(
             kinv, batch_size, n, t, tiles_n, k_i_lds, k_j_lds,
             [&](long idx) { return cload(k_ws + idx); },
             [&](int q, float v) {
@@ -712,12 +900,17 @@ extern "C" int launch_eagle_sweep(
   const int tiles_n = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
   // Grid size is a pure throughput knob (every phase is a grid-stride
   // loop and partial-sum layout is grid-independent, so results are
-  // bit-identical at any size). Measured at the headline shape
-  // (N=1000, batch 25): tiles_n^2=256 WGs -> 61 us/iter but 64-128
-  // WGs -> ~42 us/iter — the sense-reversing barrier's cost grows
-  // with arrival count, so cap the default at 128 and floor at 64
-  // (tiles_n^2 starves phase A at small N: 4 WGs at N=125 ran at
-  // 107 us/iter). Override with VIZIER_AMD_SWEEP_GRID.
+  // bit-identical at any size). The default is capped at 128 and
+  // floored at 64. The cap dates from the sense-reversing barrier,
+  // whose cost grew with the arrival count (headline shape, N=1000,
+  // batch 25: 256 WGs ran at 61 us/iter, 64-128 WGs at ~42). The
+  // barrier on one growing counter (grid_sync) no longer has that cost:
+  // the grid tables in profiles/bench_sweep_two_barriers.md and
+  // profiles/bench_sweep_loads_in_flight.md. Raising the cap is left to
+  // a change of its own, A/B'd over the other shapes;
+  // tests/test_sweep_kernel.py asserts 128. The floor: tiles_n^2
+  // starves phase A at small N (4 WGs at N=125 ran at 107 us/iter).
+  // Override with VIZIER_AMD_SWEEP_GRID.
   int grid = tiles_n * tiles_n;                   // fills phase B
   if (grid > 128) grid = 128;
   if (grid < 64) grid = 64;

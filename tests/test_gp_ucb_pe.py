@@ -333,3 +333,137 @@ class TestFusedPathGuards:
     # one UCB (new data) + jointly-optimized set members.
     assert kinds[0] == 'ucb'
     assert kinds[1:] == ['set_pe', 'set_pe']
+
+
+# -- the PE variance cache against the best fp32 cache there can be ----------
+
+
+def _variance_geometry(clustered: bool, seed: int, n=60, d=5, nq=256):
+  """(x (n, d), xq (nq, d)) fp32. clustered: half the points within 1e-3 of
+  one of them, as late in a study. Queries: half within 0.02 of a training
+  row, half uniform."""
+  g = torch.Generator().manual_seed(seed)
+  x = torch.rand(n, d, generator=g, dtype=torch.float64)
+  if clustered:
+    h = n // 2
+    x[h:] = x[0] + 1e-3 * (2.0 * torch.rand(n - h, d, generator=g,
+                                            dtype=torch.float64) - 1.0)
+  rows = torch.randint(n, (nq // 2,), generator=g)
+  near = x[rows] + 0.02 * (2.0 * torch.rand(nq // 2, d, generator=g,
+                                            dtype=torch.float64) - 1.0)
+  far = torch.rand(nq - nq // 2, d, generator=g, dtype=torch.float64)
+  return (x.clamp(0.0, 1.0).float(),
+          torch.cat([near, far]).clamp(0.0, 1.0).float())
+
+
+def _installed_posterior(x, lengthscale, noise, linear: bool):
+  """A posterior cache with chosen hyperparameters (amp 1, mean 0), built
+  the way the fit builds it; labels do not matter for a variance."""
+  from vizier_amd._src.gp import gp_model, linear_matern
+  fb = gp_model._from_bounded
+  n, d = x.shape
+  head = [fb(0.0, *gp_model._LOG_AMP_BOUNDS),
+          fb(float(np.log(noise)), *gp_model._LOG_NOISE_BOUNDS),
+          fb(0.0, *gp_model._MEAN_BOUNDS)]
+  ls = [fb(float(np.log(lengthscale)), *gp_model._LOG_LS_BOUNDS)] * d
+  y = torch.zeros(n)
+  if not linear:
+    raw = torch.tensor(head + ls, dtype=torch.float32)
+    return gp_model._build_posterior_cache(x, y, raw, 0.0,
+                                           precompute_inverse=True)
+  slope = fb(float(np.log(0.3)), *gp_model._LOG_AMP_BOUNDS)
+  raw = torch.tensor(head + [slope, 0.2] + ls, dtype=torch.float32)
+  params = linear_matern.LinearMaternParams.from_raw(raw)
+  noise_eff = max(float(params.noise), 1e-3 * float(params.amplitude) ** 2)
+  # noise_eff: as train_linear_matern_gp floors it.
+  return linear_matern.LinearMaternPosterior(
+      x=x, params=params, linear_coef=1.0, L=torch.eye(n), alpha=y, nll=0.0,
+      raw=raw, noise_eff=noise_eff)
+
+
+def _variance_statistic(post, var_post, xq):
+  """(e(stored), e(best fp32), smallest fp64-evaluated stored variance).
+
+  e(C) = max over the queries of |var_exact(C) - var_true|. var_true: fp64
+  inverse of the fp64 Gram with noise max(params.noise, noise_eff).
+  var_exact(C): the same quadform in fp64 with the fp32 cache C upcast
+  (K_inv, or L for the linear kernel). The best fp32 cache is the fp32
+  rounding of the fp64 inverse (of the fp64 Cholesky factor)."""
+  from vizier_amd._src.gp import linear_matern, matern
+  p = var_post.params
+  x64, q64 = var_post.x.double(), xq.double()
+  ls, amp = p.lengthscales.double(), p.amplitude.double()
+  noise = max(float(p.noise), float(post.noise_eff))
+  if isinstance(var_post, linear_matern.LinearMaternPosterior):
+    import dataclasses
+    p64 = dataclasses.replace(p, **{
+        f.name: getattr(p, f.name).double() for f in dataclasses.fields(p)})
+    lc = var_post.linear_coef
+    K = linear_matern._combined_gram(p64, lc, x64, None)
+    k = linear_matern._combined_gram(p64, lc, q64, x64)
+    zq = q64 / ls - lc * p64.shift
+    prior = amp ** 2 + (lc * p64.slope) ** 2 * (zq * zq).sum(-1)
+  else:
+    K = matern.gram_matern52(x64, None, ls, amp)
+    k = matern.gram_matern52(q64, x64, ls, amp)
+    prior = amp ** 2
+  K = K + noise * torch.eye(x64.shape[0], dtype=torch.float64)
+  var_true = prior - ((k @ torch.linalg.inv(K)) * k).sum(-1)
+
+  if var_post.K_inv is not None:
+    def var_exact(C):
+      return prior - ((k @ C.double()) * k).sum(-1)
+    stored, best = var_post.K_inv, torch.linalg.inv(K).float()
+  else:
+    def var_exact(C):
+      v = torch.linalg.solve_triangular(C.double(), k.T, upper=False)
+      return prior - (v * v).sum(0)
+    stored, best = var_post.L, torch.linalg.cholesky(K).float()
+  assert stored.dtype == torch.float32
+  got = var_exact(stored)
+  return (float((got - var_true).abs().max()),
+          float((var_exact(best) - var_true).abs().max()), float(got.min()))
+
+
+class TestVariancePosteriorConditioning:
+  """_variance_posterior supplies the PE score (stddev_all) and the set-PE
+  covariance. Its fp32 cache may be no worse than 4x the fp32 rounding of
+  the fp64 inverse: both round the same matrix, so a larger ratio means
+  the inverse was FORMED in low precision.
+
+  Measured (CPU), e(stored) / e(best fp32) / ratio, while the cache was
+  still built in fp32 from the unfloored noise:
+    matern  clustered 6.6e-01 / 7.0e-05 / 9.3e+03 (the jitter ladder had to
+            rescue the fp32 Cholesky), benign 3.7e-06 / 7.6e-07 / 4.9
+    linear  clustered 6.7e-03 / 6.8e-08 / 9.8e+04, benign 1.6e-06 /
+            1.0e-07 / 15.8
+  and built in fp64 with the fitted cache's noise floor: ratio 1.0 in all
+  four (the stored cache IS the fp32 rounding of the fp64 one); smallest
+  fp64-evaluated variance -3.5e-05 against an allowance of -2.8e-04.
+  """
+
+  @pytest.mark.parametrize('linear', [False, True], ids=['matern', 'linear'])
+  @pytest.mark.parametrize('clustered,lengthscale,noise,seed', [
+      (True, 3.0, 1e-6, 4101), (False, 0.5, 1e-2, 4102)],
+      ids=['clustered', 'benign'])
+  def test_cache_is_as_good_as_an_fp32_cache_can_be(
+      self, clustered, lengthscale, noise, seed, linear):
+    problem = make_problem(5)
+    designer = VizierGPUCBPEBandit(problem, UCBPEConfig(
+        device='cpu', dtype=torch.float32, mixes_linear_kernel=linear))
+    x, xq = _variance_geometry(clustered, seed)
+    post = _installed_posterior(x, lengthscale, noise, linear)
+    designer._posterior = post
+    var_post = designer._variance_posterior(post.x)
+    assert var_post.x is post.x
+    assert type(var_post) is type(post)
+    assert var_post.alpha.dtype == torch.float32
+    assert not bool(var_post.alpha.any())
+    e_stored, e_best, var_min = _variance_statistic(post, var_post, xq)
+    print(f'OBSERVED variance cache {"linear" if linear else "matern"} '
+          f'{"clustered" if clustered else "benign"}: e(stored) '
+          f'{e_stored:.3e}, e(best fp32) {e_best:.3e}, ratio '
+          f'{e_stored / e_best:.3g}, min variance {var_min:.3e}')
+    assert e_best > 0.0
+    assert e_stored <= 4.0 * e_best
+    assert var_min >= -4.0 * e_best

@@ -320,33 +320,47 @@ class VizierGPUCBPEBandit(Designer):
     """GP conditioned on all (completed+hallucinated) features.
 
     Only the predictive variance is used, so alpha is zeros.
+
+    Built as gp_model._build_posterior_cache builds the fitted cache:
+    Gram, Cholesky and inverse in float64 with the noise the fitted cache
+    was floored at (posterior.noise_eff), stored in the working dtype.
+    The stddev this cache yields IS the PE score; an fp32 inverse of a
+    late-study Gram (clustered points, fitted noise near its lower bound)
+    returns negative variances. x stays the x_all OBJECT: _fusable
+    compares data_ptr.
     """
     posterior = posterior if posterior is not None else self._posterior
     params = posterior.params
     from vizier_amd._src.gp.matern import gram_matern52
     n = x_all.shape[0]
     from vizier_amd._src.gp import linear_matern
+    x64 = x_all.double()
+    p64 = dataclasses.replace(params, **{
+        f.name: torch.as_tensor(getattr(params, f.name),
+                                device=x_all.device).double()
+        for f in dataclasses.fields(params)})
+    noise_eff = max(float(params.noise),
+                    float(getattr(posterior, 'noise_eff', 0.0)))
+    noise_eye = noise_eff * torch.eye(n, dtype=x64.dtype,
+                                      device=x_all.device)
+    alpha = torch.zeros(n, dtype=x_all.dtype, device=x_all.device)
     if isinstance(posterior, linear_matern.LinearMaternPosterior):
       lc = posterior.linear_coef
-      K = linear_matern._combined_gram(params, lc, x_all, None)
-      K = K + params.noise * torch.eye(n, dtype=x_all.dtype,
-                                       device=x_all.device)
-      L = gp_model.cholesky_with_jitter(K, params.amplitude ** 2)
+      K = linear_matern._combined_gram(p64, lc, x64, None) + noise_eye
+      L64 = gp_model.cholesky_with_jitter(K, p64.amplitude ** 2)
       return linear_matern.LinearMaternPosterior(
-          x=x_all, params=params, linear_coef=lc, L=L,
-          alpha=torch.zeros(n, dtype=x_all.dtype, device=x_all.device),
-          nll=0.0)
-    K = gram_matern52(x_all, None, params.lengthscales, params.amplitude)
-    K = K + params.noise * torch.eye(n, dtype=x_all.dtype,
-                                     device=x_all.device)
-    L = gp_model.cholesky_with_jitter(K, params.amplitude ** 2)
-    eye = torch.eye(n, dtype=x_all.dtype, device=x_all.device)
-    z = torch.linalg.solve_triangular(L, eye, upper=False)
-    K_inv = z.T @ z
+          x=x_all, params=params, linear_coef=lc, L=L64.to(x_all.dtype),
+          alpha=alpha, nll=0.0, noise_eff=noise_eff)
+    K = gram_matern52(x64, None, p64.lengthscales, p64.amplitude) + noise_eye
+    L64 = gp_model.cholesky_with_jitter(K, p64.amplitude ** 2)
+    eye = torch.eye(n, dtype=x64.dtype, device=x_all.device)
+    if n >= gp_model._NO_GRAD_FIT_N:
+      z = gp_model._blocked_solve_lower(L64, eye)
+    else:
+      z = torch.linalg.solve_triangular(L64, eye, upper=False)
     return gp_model.GPPosterior(
-        x=x_all, params=params, L=L,
-        alpha=torch.zeros(n, dtype=x_all.dtype, device=x_all.device),
-        K_inv=K_inv, nll=0.0)
+        x=x_all, params=params, L=L64.to(x_all.dtype), alpha=alpha,
+        K_inv=(z.T @ z).to(x_all.dtype), nll=0.0, noise_eff=noise_eff)
 
   def _optimize_set(self, x_all: torch.Tensor, q: int) -> torch.Tensor:
     """Jointly optimizes q exploration points via the SET-PE acquisition.
@@ -467,6 +481,41 @@ class VizierGPUCBPEBandit(Designer):
 
   def _optimize_one(self, use_ucb: bool, x_all: torch.Tensor
                     ) -> torch.Tensor:
+    cfg = self._config
+    score_fn = self._one_score_fn(use_ucb, x_all)
+    factory = VectorizedOptimizerFactory(
+        eagle_config=EagleStrategyConfig(),
+        max_evaluations=cfg.max_evaluations,
+        suggestion_batch_size=cfg.suggestion_batch_size)
+    optimizer = factory(
+        n_continuous=self._codec.n_continuous,
+        categorical_sizes=self._codec.categorical_sizes,
+        seed=self._seed + len(self._completed) + x_all.shape[0],
+        device=self._device, dtype=cfg.dtype)
+
+    if self._mo_posteriors is not None:
+      # Eagle prior seeding needs scalar rewards: use the scalarized
+      # warped labels (same scalarizer as the UCB phase).
+      with torch.no_grad():
+        rewards = self._mo_scalarizer(
+            self._warped_labels).mean(dim=0).cpu().numpy()
+    else:
+      rewards = self._warped_labels.cpu().numpy()
+    prior_features, prior_rewards = trials_to_sorted_features(
+        self._converter, self._codec, self._completed, rewards,
+        device=self._device, dtype=cfg.dtype)
+    results = optimizer.optimize(score_fn, count=1,
+                                 prior_features=prior_features,
+                                 prior_rewards=prior_rewards)
+    return self._codec.decode(results.features)[0, 0, :]
+
+  def _one_score_fn(self, use_ucb: bool, x_all: torch.Tensor):
+    """The scorer of `_optimize_one`: CandidateBatch (B, 1, .) -> (B,).
+
+    UCB (use_ucb) or PE, single- or multi-metric, with the trust region
+    anchored on x_all (completed + pending). Carries `graph_safe`, or
+    `scoring` and `codec_identity` on the pure-HIP UCB path.
+    """
     cfg = self._config
     posterior = self._posterior
     trust_region = acq_lib.TrustRegion.for_converter(
@@ -669,29 +718,4 @@ class VizierGPUCBPEBandit(Designer):
             scores = trust_region.apply(xs, scores)
           return scores
         score_fn.graph_safe = False  # float(tensor) syncs in predict
-
-    factory = VectorizedOptimizerFactory(
-        eagle_config=EagleStrategyConfig(),
-        max_evaluations=cfg.max_evaluations,
-        suggestion_batch_size=cfg.suggestion_batch_size)
-    optimizer = factory(
-        n_continuous=self._codec.n_continuous,
-        categorical_sizes=self._codec.categorical_sizes,
-        seed=self._seed + len(self._completed) + x_all.shape[0],
-        device=self._device, dtype=cfg.dtype)
-
-    if self._mo_posteriors is not None:
-      # Eagle prior seeding needs scalar rewards: use the scalarized
-      # warped labels (same scalarizer as the UCB phase).
-      with torch.no_grad():
-        rewards = self._mo_scalarizer(
-            self._warped_labels).mean(dim=0).cpu().numpy()
-    else:
-      rewards = self._warped_labels.cpu().numpy()
-    prior_features, prior_rewards = trials_to_sorted_features(
-        self._converter, self._codec, self._completed, rewards,
-        device=self._device, dtype=cfg.dtype)
-    results = optimizer.optimize(score_fn, count=1,
-                                 prior_features=prior_features,
-                                 prior_rewards=prior_rewards)
-    return self._codec.decode(results.features)[0, 0, :]
+    return score_fn

@@ -115,6 +115,7 @@ class LinearMaternPosterior:
   nll: float
   raw: Optional[torch.Tensor] = None
   aux: Optional[torch.Tensor] = None  # [slope, shift] for broadcasts
+  noise_eff: float = 0.0     # cache noise floor actually used
 
   @property
   def K_inv(self):
@@ -186,4 +187,5 @@ def train_linear_matern_gp(
       alpha=alpha.to(x.dtype), nll=float(best_f[idx]),
       raw=raw.detach(),
       aux=torch.stack([params.slope.reshape(()),
-                       params.shift.reshape(())]))
+                       params.shift.reshape(())]),
+      noise_eff=float(noise_eff))

@@ -40,7 +40,8 @@
 // Resident: every workgroup that owns a candidate (blockIdx.x <
 // batch_size) loads pool, rewards, perturbations and best_reward once at
 // kernel start into LDS (the upper half of pool_lds, which phase B's
-// k_i / k_j staging does not touch, plus st_rewards / st_perts / st_best)
+// k_i / k_j staging does not touch: half 0 stages in the lower half and
+// half 1 in stage1_lds; plus st_rewards / st_perts / st_best)
 // and keeps them for the whole launch. RC = reduce + scores + update:
 // each owner applies the update of ALL batch_size fireflies, with the
 // logic and RNG indices of the legacy phase C, to its own copy. The
@@ -71,13 +72,51 @@
 // candidate i updates firefly i in C, and a barrier separates C from the
 // next A.
 //
+// Workgroup shape: 512 threads, eight waves, two per SIMD, on at most 128
+// workgroups (the barrier's cost grows with the arrivals on its one word,
+// so the second tile of a CU comes from more waves, not more workgroups).
+// Phase B gives each half of 256 threads a tile and a staging area of its
+// own (half 0 the lower half of pool_lds, half 1 stage1_lds): tile
+// blockIdx.x + G * (2 * trip + half). A lone wave issues fp32 fma at half
+// the SIMD's rate and nothing covers its LDS and L2 waits; two waves per
+// SIMD cover each other's. Which half computes a tile partial does not
+// change its operations or their order. Phases A, B2 and C / RC are the
+// 256-thread arithmetic of the step kernels on half 0 (same rows per
+// thread, same chains, same 4-wave reduction order: sweep_block_reduce);
+// the `+= BLOCK` loops of a half-1 thread start at SWEEP_IDLE and make no
+// trip, and tests like tid == 0 are false for it.
+//
+// Every __syncthreads must be reached by all eight waves, so none stands
+// under a condition that differs within a workgroup. The sites, and why:
+//   grid_sync (two each)       called at the top level of the iteration
+//                              loop, under the grid-uniform `fold` and
+//                              `resident` only
+//   sweep_block_reduce[2]      called from the sites below, unconditionally
+//   prologue state load        under resident && owner: owner is
+//                              blockIdx.x < batch_size
+//   phase A                    all inside the loop over b = blockIdx.x +
+//                              k G, straight-line except `stage_pool`
+//                              (grid-uniform)
+//   vz_quadform_tile_pipelined two, outside `if (live)`; the trip loop
+//                              runs on tile0 = blockIdx.x + 2 G trip, the
+//                              same for both halves
+//   phase B2                   loop over q = blockIdx.x + k G
+//   RC                         under resident && owner; `half == 0` guards
+//                              only reduce_all_partials, which has none
+//   legacy C                   under fold && owner, then the loop over
+//                              i = blockIdx.x + k G
+// Conditions on `half`, `live`, `tid` or `lane` enclose loads, stores and
+// arithmetic only.
+//
 // Scope: continuous-only spaces, q == 1 (the flagship GP-Bandit
 // config); the optimizer falls back to the hipGraph path otherwise.
 //
 // Determinism: phases replicate the standalone kernels VERBATIM (same
 // counter-based RNG streams, same 64x64 tile quadform and partial
 // order, same block-reduce orders; where a loop is restructured to keep
-// its loads in flight, vz_quadform_tile_pipelined and sweep_kvec below,
+// its loads in flight, vz_quadform_tile_pipelined, sweep_kvec and the
+// chunked loops of phase A's suggest step below, or two reductions share
+// one barrier pass (sweep_block_reduce2),
 // every value still comes from the same operations on the same operands
 // in the same order), so for N < 4096 the sweep is
 // BIT-IDENTICAL to the step kernels of the hipGraph path for the same
@@ -99,7 +138,14 @@
 
 #include "common.h"
 
+// The workgroup has SWEEP_THREADS threads: two halves of BLOCK. Phase B
+// runs one tile per half; every other phase is the BLOCK-thread arithmetic
+// of the step kernels on half 0 (waves 0..3), with half 1 predicated off.
 #define BLOCK 256
+#define SWEEP_THREADS (2 * BLOCK)
+// Loop start of a half-1 thread in the BLOCK-thread phases: past every
+// bound (all are below 2^24), and + 4 * BLOCK does not overflow.
+#define SWEEP_IDLE (1 << 30)
 #define MAX_POOL 128
 #define SWEEP_NCHUNK 10   // must match posterior_score.hip's NCHUNK
 #define POOL_LDS_CAP 8192  // floats: stage pool in LDS when it fits
@@ -165,6 +211,62 @@ __device__ __forceinline__ void grid_sync(unsigned int* bar,
     asm volatile("" ::: "memory");
   }
   __syncthreads();
+}
+
+// block_reduce (common.h) for the sweep's eight-wave workgroup: the shuffle
+// tree per wave, then the 4-lane second stage over waves 0..3 only, in
+// block_reduce's order for a 256-thread block. Waves 4..7 run the shuffles
+// on a value nobody reads, store nothing (lds4[4..6] hold other scalars)
+// and take the __syncthreads. Result valid in thread 0.
+template <typename T, typename Op>
+__device__ __forceinline__ T sweep_block_reduce(T v, T* lds4, Op op,
+                                                T init) {
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = threadIdx.x / WAVE_SIZE;
+#pragma unroll
+  for (int offset = WAVE_SIZE / 2; offset > 0; offset >>= 1) {
+    v = op(v, __shfl_down(v, offset, WAVE_SIZE));
+  }
+  if (lane == 0 && wave < BLOCK / WAVE_SIZE) lds4[wave] = v;
+  __syncthreads();
+  if (wave == 0) {
+    v = (lane < BLOCK / WAVE_SIZE) ? lds4[lane] : init;
+#pragma unroll
+    for (int offset = 2; offset > 0; offset >>= 1) {
+      v = op(v, __shfl_down(v, offset, WAVE_SIZE));
+    }
+  }
+  return v;
+}
+
+// Two reductions on one barrier pass: each value goes through
+// sweep_block_reduce's shuffles and second stage on its own, with its own
+// LDS slots, so each result has the bits of a reduction of its own; only
+// the __syncthreads is shared. Results in place, valid in thread 0.
+template <typename T, typename Op1, typename Op2>
+__device__ __forceinline__ void sweep_block_reduce2(
+    T& v1, T& v2, T* lds4a, T* lds4b, Op1 op1, Op2 op2, T init1, T init2) {
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = threadIdx.x / WAVE_SIZE;
+#pragma unroll
+  for (int offset = WAVE_SIZE / 2; offset > 0; offset >>= 1) {
+    v1 = op1(v1, __shfl_down(v1, offset, WAVE_SIZE));
+    v2 = op2(v2, __shfl_down(v2, offset, WAVE_SIZE));
+  }
+  if (lane == 0 && wave < BLOCK / WAVE_SIZE) {
+    lds4a[wave] = v1;
+    lds4b[wave] = v2;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    v1 = (lane < BLOCK / WAVE_SIZE) ? lds4a[lane] : init1;
+    v2 = (lane < BLOCK / WAVE_SIZE) ? lds4b[lane] : init2;
+#pragma unroll
+    for (int offset = 2; offset > 0; offset >>= 1) {
+      v1 = op1(v1, __shfl_down(v1, offset, WAVE_SIZE));
+      v2 = op2(v2, __shfl_down(v2, offset, WAVE_SIZE));
+    }
+  }
 }
 
 // Tile partials at or below which phase C reduces them itself (N <= 2048:
@@ -238,28 +340,35 @@ __device__ __forceinline__ float fold_quad(const float* wp, int q) {
 // The sweep's own form of vz_quadform_tile (common.h): every partial is
 // produced by the same operations on the same operands in the same order,
 // so the two stay bit-identical; only when the loads are issued differs.
-// The kernel runs one wave per SIMD, so no other wave hides a wait, and
-// the shared routine's staging loop exposes one memory-side round trip per
+// The shared routine's staging loop exposes one memory-side round trip per
 // load (the guarded ternary around the relaxed atomic load keeps the
 // compiler from batching them): 16 dependent round trips per tile. Here a
 // thread puts its 16 loads of k_i / k_j in flight before the first wait.
 // Elements outside the batch or the tile re-read a clamped address and
 // are replaced by the zero the shared routine stores; a branch around the
 // load would bring the waits back.
+//
+// Called by all SWEEP_THREADS threads, once per trip of phase B. Each half
+// of the workgroup (BLOCK threads: `tid` is the thread's index within its
+// half, 0 .. BLOCK - 1, the shared routine's threadIdx.x) works on a tile
+// and a staging area of its own, so two tiles are in flight per workgroup
+// and two waves share each SIMD, each covering the other's LDS and L2
+// waits. `live` is uniform over a half: a half without a tile in this trip
+// does no loads and no stores, but takes both __syncthreads, which stand
+// outside every condition.
 template <typename LoadK, typename StoreP>
 __device__ __forceinline__ void vz_quadform_tile_pipelined(
     const float* __restrict__ kinv, int b, int n, int tile, int tiles_n,
-    float* k_i_lds, float* k_j_lds, LoadK loadk, StoreP store,
-    unsigned long long* prof = nullptr) {
+    int tid, bool live, float* k_i_lds, float* k_j_lds, LoadK loadk,
+    StoreP store, unsigned long long* prof = nullptr) {
   constexpr int kStage = VZ_QF_QMAX * VZ_QF_TILE / BLOCK;  // 8 per thread
-  const int tid = threadIdx.x;
-  const bool profme = (prof != nullptr && tid == 0);
+  const bool profme = (prof != nullptr && threadIdx.x == 0);
   unsigned long long tq0 = profme ? wall_clock64() : 0;
   const int ti = tile / tiles_n, tj = tile % tiles_n;
   const int i0 = ti * VZ_QF_TILE, j0 = tj * VZ_QF_TILE;
   const int ilen = min(VZ_QF_TILE, n - i0);
   const int jlen = min(VZ_QF_TILE, n - j0);
-  {
+  if (live) {
     // e = tid + u * BLOCK: the column c is the same for every u.
     const int c = tid % VZ_QF_TILE;
     const int q0 = tid / VZ_QF_TILE;
@@ -279,54 +388,56 @@ __device__ __forceinline__ void vz_quadform_tile_pipelined(
       k_j_lds[tid + u * BLOCK] = (inq && c < jlen) ? rj[u] : 0.0f;
     }
   }
-  __syncthreads();
+  __syncthreads();  // all eight waves, live or not
   if (profme) {
     const unsigned long long tq1 = wall_clock64();
     prof[0] += tq1 - tq0;
     tq0 = tq1;
   }
-  const int wave = tid / WAVE_SIZE;
-  const int lane = tid % WAVE_SIZE;
-  float acc[8];
+  if (live) {
+    const int wave = tid / WAVE_SIZE;
+    const int lane = tid % WAVE_SIZE;
+    float acc[8];
 #pragma unroll
-  for (int qq = 0; qq < 8; ++qq) acc[qq] = 0.0f;
-  if (lane < jlen) {
-    if (ilen == VZ_QF_TILE) {
-      for (int ib = 0; ib < VZ_QF_TILE; ib += 8) {
-        float kvv[8];
+    for (int qq = 0; qq < 8; ++qq) acc[qq] = 0.0f;
+    if (lane < jlen) {
+      if (ilen == VZ_QF_TILE) {
+        for (int ib = 0; ib < VZ_QF_TILE; ib += 8) {
+          float kvv[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          kvv[u] = kinv[(long)(i0 + ib + u) * n + j0 + lane];
+          for (int u = 0; u < 8; ++u) {
+            kvv[u] = kinv[(long)(i0 + ib + u) * n + j0 + lane];
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+#pragma unroll
+            for (int qq = 0; qq < 8; ++qq) {
+              acc[qq] = fmaf(
+                  k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + ib + u],
+                  kvv[u], acc[qq]);
+            }
+          }
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
+      } else {
+        for (int i = 0; i < ilen; ++i) {
+          const float kv = kinv[(long)(i0 + i) * n + j0 + lane];
 #pragma unroll
           for (int qq = 0; qq < 8; ++qq) {
-            acc[qq] = fmaf(
-                k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + ib + u],
-                kvv[u], acc[qq]);
+            acc[qq] = fmaf(k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + i], kv,
+                           acc[qq]);
           }
         }
       }
-    } else {
-      for (int i = 0; i < ilen; ++i) {
-        const float kv = kinv[(long)(i0 + i) * n + j0 + lane];
+    }
 #pragma unroll
-        for (int qq = 0; qq < 8; ++qq) {
-          acc[qq] = fmaf(k_i_lds[(wave * 8 + qq) * VZ_QF_TILE + i], kv,
-                         acc[qq]);
-        }
-      }
+    for (int qq = 0; qq < 8; ++qq) {
+      const int q = wave * 8 + qq;
+      float v = acc[qq] * k_j_lds[q * VZ_QF_TILE + lane];
+      v = wave_reduce_sum(v);
+      if (lane == 0 && q < b) store(q, v);
     }
   }
-#pragma unroll
-  for (int qq = 0; qq < 8; ++qq) {
-    const int q = wave * 8 + qq;
-    float v = acc[qq] * k_j_lds[q * VZ_QF_TILE + lane];
-    v = wave_reduce_sum(v);
-    if (lane == 0 && q < b) store(q, v);
-  }
-  __syncthreads();
+  __syncthreads();  // all eight waves, live or not
   if (profme) prof[1] += wall_clock64() - tq0;
 }
 
@@ -357,13 +468,17 @@ __device__ __forceinline__ float sweep_matern52(float d2) {
 // dimensions past dc re-read a clamped address and are discarded.
 #define KV_ROWS 4
 #define KV_CHUNK 4
+// Phase A's suggest step: dimensions per chunk of the squared distance,
+// fireflies per chunk of the weighted sum.
+#define SG_DCHUNK 8
+#define SG_PCHUNK 16
 
 template <bool VEC4>
 __device__ __forceinline__ void sweep_kvec(
     const float* __restrict__ x, const float* __restrict__ inv_ls,
     const float* __restrict__ alpha, const float* xq_lds, float* k_row,
-    int dc, int n, float amp2, float& mu_acc, float& min_linf) {
-  for (int row0 = threadIdx.x; row0 < n; row0 += KV_ROWS * BLOCK) {
+    int dc, int n, int wt, float amp2, float& mu_acc, float& min_linf) {
+  for (int row0 = wt; row0 < n; row0 += KV_ROWS * BLOCK) {
     const float* xr[KV_ROWS];
     float al[KV_ROWS];
 #pragma unroll
@@ -424,7 +539,7 @@ __device__ __forceinline__ void sweep_kvec(
   }
 }
 
-extern "C" __global__ __launch_bounds__(BLOCK) void
+extern "C" __global__ __launch_bounds__(SWEEP_THREADS) void
 eagle_sweep_kernel(
     float* __restrict__ pool_cont,         // (P, Dc)   [coherent]
     float* __restrict__ rewards,           // (P,)      [coherent]
@@ -452,15 +567,25 @@ eagle_sweep_kernel(
     float tr_radius) {
   __shared__ float scale[MAX_POOL];
   __shared__ float red[8];
+  __shared__ float red2[4];  // second value of sweep_block_reduce2
   __shared__ float s_scalar;
   __shared__ __attribute__((aligned(16))) float xq_lds[512];
   __shared__ float pool_lds[POOL_LDS_CAP];
+  // Phase B's k_i / k_j staging of half 1 (half 0 stages in pool_lds).
+  __shared__ float stage1_lds[2 * VZ_QF_QMAX * VZ_QF_TILE];
   // Resident mode: this workgroup's private copy of the Eagle state.
   __shared__ float st_rewards[MAX_POOL];
   __shared__ float st_perts[MAX_POOL];
   __shared__ float st_best;
 
   const int tid = threadIdx.x;
+  // Half of the workgroup (wave-uniform) and the thread's index in it.
+  const int half = tid / BLOCK;
+  const int htid = tid % BLOCK;
+  // Start of every `+= BLOCK` loop of the BLOCK-thread phases: half 1
+  // makes no trip. Tests like tid == 0 and tid < batch_size are false for
+  // half 1 as they stand.
+  const int wt = half == 0 ? tid : SWEEP_IDLE;
   const int G = gridDim.x;
   const int pool_elems = pool_size * dc;
   // All three are grid-uniform: every workgroup takes the same barriers.
@@ -496,8 +621,8 @@ eagle_sweep_kernel(
   // Resident mode: the state was written by earlier launches, so plain
   // loads see it; from here on only this workgroup touches its copy.
   if (resident && owner) {
-    for (int e = tid; e < pool_elems; e += BLOCK) st_pool[e] = pool_cont[e];
-    for (int p = tid; p < pool_size; p += BLOCK) {
+    for (int e = wt; e < pool_elems; e += BLOCK) st_pool[e] = pool_cont[e];
+    for (int p = wt; p < pool_size; p += BLOCK) {
       st_rewards[p] = rewards[p];
       st_perts[p] = perturbations[p];
     }
@@ -518,7 +643,7 @@ eagle_sweep_kernel(
     // ---- Phase A: suggest + k-vec (workgroup owns candidate b) ----
     for (int b = blockIdx.x; b < batch_size; b += G) {
       if (stage_pool) {
-        for (int e = tid; e < pool_elems; e += BLOCK) {
+        for (int e = wt; e < pool_elems; e += BLOCK) {
           pool_lds[e] = cload(pool_cont + e);
         }
         __syncthreads();
@@ -528,20 +653,32 @@ eagle_sweep_kernel(
                                        : cload(rewards + me);
       const float my_pert = resident ? st_perts[me]
                                      : cload(perturbations + me);
-      for (int p = tid; p < pool_size; p += BLOCK) {
+      // Squared distance over SG_DCHUNK dimensions at a time: the loads
+      // of a chunk (LDS, or memory-side when the pool is not staged) are
+      // issued together, then the chain runs j = 0 .. dc - 1 as in the
+      // step kernel. Dimensions past dc re-read dc - 1 and are dropped.
+      auto dist2 = [&](auto ld, int p) {
         float d2 = 0.0f;
-        if (pool_in_lds) {
-          for (int j = 0; j < dc; ++j) {
-            const float diff = pl[me * dc + j] - pl[p * dc + j];
-            d2 = fmaf(diff, diff, d2);
+        for (int j0 = 0; j0 < dc; j0 += SG_DCHUNK) {
+          float mv[SG_DCHUNK], pv[SG_DCHUNK];
+#pragma unroll
+          for (int u = 0; u < SG_DCHUNK; ++u) {
+            const int jc = min(j0 + u, dc - 1);
+            mv[u] = ld(me * dc + jc);
+            pv[u] = ld(p * dc + jc);
           }
-        } else {
-          for (int j = 0; j < dc; ++j) {
-            const float diff = cload(pool_cont + me * dc + j) -
-                               cload(pool_cont + p * dc + j);
-            d2 = fmaf(diff, diff, d2);
+#pragma unroll
+          for (int u = 0; u < SG_DCHUNK; ++u) {
+            const float diff = mv[u] - pv[u];
+            d2 = (j0 + u < dc) ? fmaf(diff, diff, d2) : d2;
           }
         }
+        return d2;
+      };
+      auto ld_lds = [&](int idx) { return pl[idx]; };
+      auto ld_mem = [&](int idx) { return cload(pool_cont + idx); };
+      for (int p = wt; p < pool_size; p += BLOCK) {
+        const float d2 = pool_in_lds ? dist2(ld_lds, p) : dist2(ld_mem, p);
         const float reward_p = resident ? st_rewards[p]
                                         : cload(rewards + p);
         const float dir = (reward_p - my_reward >= 0.0f) ? gravity
@@ -553,20 +690,22 @@ eagle_sweep_kernel(
       }
       __syncthreads();
       float pulls = 0.0f, pushes = 0.0f;
-      for (int p = tid; p < pool_size; p += BLOCK) {
+      for (int p = wt; p < pool_size; p += BLOCK) {
         pulls += (scale[p] > 0.0f) ? 1.0f : 0.0f;
         pushes += (scale[p] < 0.0f) ? 1.0f : 0.0f;
       }
-      float n_pull = block_reduce(pulls, red, fsum, 0.0f);
-      if (tid == 0) red[4] = fmaxf(n_pull, 1.0f);
-      __syncthreads();
-      float n_push = block_reduce(pushes, red, fsum, 0.0f);
-      if (tid == 0) red[5] = fmaxf(n_push, 1.0f);
+      // Both counts on one barrier pass (red / red2), each in
+      // block_reduce's order.
+      sweep_block_reduce2(pulls, pushes, red, red2, fsum, fsum, 0.0f, 0.0f);
+      if (tid == 0) {
+        red[4] = fmaxf(pulls, 1.0f);
+        red[5] = fmaxf(pushes, 1.0f);
+      }
       __syncthreads();
       const float inv_pull = 1.0f / red[4];
       const float inv_push = 1.0f / red[5];
       float ssum = 0.0f;
-      for (int p = tid; p < pool_size; p += BLOCK) {
+      for (int p = wt; p < pool_size; p += BLOCK) {
         const float s = scale[p];
         const float ns = norm_scale * (s > 0.0f ? s * inv_pull
                                                 : s * inv_push);
@@ -574,21 +713,34 @@ eagle_sweep_kernel(
         ssum += ns;
       }
       __syncthreads();
-      float scale_sum = block_reduce(ssum, red, fsum, 0.0f);
+      float scale_sum = sweep_block_reduce(ssum, red, fsum, 0.0f);
       if (tid == 0) s_scalar = scale_sum;
       __syncthreads();
       scale_sum = s_scalar;
-      for (int j = tid; j < dc; j += BLOCK) {
+      // The weighted sum over SG_PCHUNK fireflies at a time, chain in
+      // the order p = 0 .. pool_size - 1; fireflies past the pool re-read
+      // the last one and are dropped.
+      auto moved_of = [&](auto ld, int j) {
         float moved = 0.0f;
-        if (pool_in_lds) {
-          for (int p = 0; p < pool_size; ++p) {
-            moved = fmaf(scale[p], pl[p * dc + j], moved);
+        for (int p0 = 0; p0 < pool_size; p0 += SG_PCHUNK) {
+          float sv[SG_PCHUNK], pv[SG_PCHUNK];
+#pragma unroll
+          for (int u = 0; u < SG_PCHUNK; ++u) {
+            const int pc = min(p0 + u, pool_size - 1);
+            sv[u] = scale[pc];
+            pv[u] = ld(pc * dc + j);
           }
-        } else {
-          for (int p = 0; p < pool_size; ++p) {
-            moved = fmaf(scale[p], cload(pool_cont + p * dc + j), moved);
+#pragma unroll
+          for (int u = 0; u < SG_PCHUNK; ++u) {
+            moved = (p0 + u < pool_size) ? fmaf(sv[u], pv[u], moved)
+                                         : moved;
           }
         }
+        return moved;
+      };
+      for (int j = wt; j < dc; j += BLOCK) {
+        float moved = pool_in_lds ? moved_of(ld_lds, j)
+                                  : moved_of(ld_mem, j);
         const float mine = pool_in_lds ? pl[me * dc + j]
                                        : cload(pool_cont + me * dc + j);
         moved = mine + (moved - mine * scale_sum);
@@ -607,21 +759,21 @@ eagle_sweep_kernel(
       float min_linf = INFINITY;
       if (x_vec4) {
         sweep_kvec<true>(x, inv_ls, alpha, xq_lds, k_ws + (long)b * n, dc,
-                         n, amp2, mu_acc, min_linf);
+                         n, wt, amp2, mu_acc, min_linf);
       } else {
         sweep_kvec<false>(x, inv_ls, alpha, xq_lds, k_ws + (long)b * n, dc,
-                          n, amp2, mu_acc, min_linf);
+                          n, wt, amp2, mu_acc, min_linf);
       }
-      float mu = block_reduce(mu_acc, red, fsum, 0.0f);
+      // mu and dist on one barrier pass, as the two counts above.
+      sweep_block_reduce2(mu_acc, min_linf, red, red2, fsum, fmin_, 0.0f,
+                          INFINITY);
       if (tid == 0) {
-        cstore(mu_ws + b, mu);
-        if (resident) cstore(slot_mu + b, mu);
-      }
-      __syncthreads();
-      float dist = block_reduce(min_linf, red, fmin_, INFINITY);
-      if (tid == 0) {
-        cstore(dist_ws + b, dist);
-        if (resident) cstore(slot_dist + b, dist);
+        cstore(mu_ws + b, mu_acc);
+        cstore(dist_ws + b, min_linf);
+        if (resident) {
+          cstore(slot_mu + b, mu_acc);
+          cstore(slot_dist + b, min_linf);
+        }
       }
       __syncthreads();
     }
@@ -638,12 +790,20 @@ eagle_sweep_kernel(
     {
       const int tiles_n = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
       const int total_tiles = tiles_n * tiles_n;
-      float* k_i_lds = pool_lds;                       // 2048 floats
-      float* k_j_lds = pool_lds + VZ_QF_QMAX * VZ_QF_TILE;
-      for (int tile = blockIdx.x; tile < total_tiles; tile += G) {
-        const int t = tile;
+      // Half h stages k_i / k_j (2048 floats each) in an area of its own
+      // and takes tile blockIdx.x + G * (2 * trip + h): the tiles of a
+      // trip go to the half-0s of all workgroups first, so the halves of
+      // one workgroup are two waves per SIMD only once every CU of the
+      // grid has a tile. The trip count is the same for every wave of the
+      // grid-stride loop; a half past the last tile runs the trip with
+      // live == false (the routine's barriers are unconditional).
+      float* k_i_lds = half == 0 ? pool_lds : stage1_lds;
+      float* k_j_lds = k_i_lds + VZ_QF_QMAX * VZ_QF_TILE;
+      for (int tile0 = blockIdx.x; tile0 < total_tiles; tile0 += 2 * G) {
+        const int t = tile0 + half * G;
         vz_quadform_tile_pipelined(
-            kinv, batch_size, n, t, tiles_n, k_i_lds, k_j_lds,
+            kinv, batch_size, n, t, tiles_n, htid, t < total_tiles,
+            k_i_lds, k_j_lds,
             [&](long idx) { return cload(k_ws + idx); },
             [&](int q, float v) {
               cstore(var_ws + (long)q * (total_tiles + 1) + t, v);
@@ -664,10 +824,10 @@ eagle_sweep_kernel(
     if (!fold) {
       for (int q = blockIdx.x; q < batch_size; q += G) {
         float sacc = 0.0f;
-        for (int w = tid; w < total_tiles_c; w += BLOCK) {
+        for (int w = wt; w < total_tiles_c; w += BLOCK) {
           sacc += cload(var_ws + (long)q * (total_tiles_c + 1) + w);
         }
-        float total = block_reduce(sacc, red, fsum, 0.0f);
+        float total = sweep_block_reduce(sacc, red, fsum, 0.0f);
         if (tid == 0) {
           cstore(var_ws + (long)q * (total_tiles_c + 1) + total_tiles_c,
                  total);
@@ -702,7 +862,7 @@ eagle_sweep_kernel(
           mu_t = cload(slot_mu + tid);
           dist_t = cload(slot_dist + tid);
         }
-        if (fold) {
+        if (fold && half == 0) {
           reduce_all_partials(var_ws, batch_size, total_tiles_c, wp);
         }
         __syncthreads();
@@ -729,7 +889,7 @@ eagle_sweep_kernel(
         }
         __syncthreads();
         const float new_best = s_scalar;
-        for (int e = tid; e < batch_size * dc; e += BLOCK) {
+        for (int e = wt; e < batch_size * dc; e += BLOCK) {
           const int i = e / dc;
           const int me = batch_start + i;
           const int ej = me * dc + (e - i * dc);
@@ -777,7 +937,9 @@ eagle_sweep_kernel(
       // next A. Folded: an owning workgroup reduces the partials of all
       // candidates once.
       if (fold && owner) {
-        reduce_all_partials(var_ws, batch_size, total_tiles_c, wp);
+        if (half == 0) {
+          reduce_all_partials(var_ws, batch_size, total_tiles_c, wp);
+        }
         __syncthreads();
       }
       for (int i = blockIdx.x; i < batch_size; i += G) {
@@ -785,7 +947,7 @@ eagle_sweep_kernel(
         // partials (cheap, deterministic, removes a barrier).
         float local_max = -INFINITY;
         float my_score = -INFINITY;
-        for (int t = tid; t < batch_size; t += BLOCK) {
+        for (int t = wt; t < batch_size; t += BLOCK) {
           float* reduced =
               var_ws + (long)t * (total_tiles_c + 1) + total_tiles_c;
           float quad;
@@ -801,7 +963,7 @@ eagle_sweep_kernel(
           local_max = fmaxf(local_max, score);
           if (t == i) my_score = score;
         }
-        float batch_max = block_reduce(local_max, red, fmax_, -INFINITY);
+        float batch_max = sweep_block_reduce(local_max, red, fmax_, -INFINITY);
         // my_score lives in the thread with tid == i%BLOCK (B <= BLOCK):
         // broadcast through LDS.
         if (tid == (i % BLOCK) && i < BLOCK) red[6] = my_score;
@@ -822,12 +984,12 @@ eagle_sweep_kernel(
         const bool dead = (pert < perturbation_lower_bound) &&
                           (reward != new_best);
         if (improved) {
-          for (int j = tid; j < dc; j += BLOCK) {
+          for (int j = wt; j < dc; j += BLOCK) {
             cstore(pool_cont + me * dc + j, out_cont[i * dc + j]);
           }
         }
         if (dead) {
-          for (int j = tid; j < dc; j += BLOCK) {
+          for (int j = wt; j < dc; j += BLOCK) {
             cstore(pool_cont + me * dc + j,
                    vz_rng_uniform<float>(seed_update, offset ^ 0x5151ull,
                                   (unsigned)(me * dc + j)));
@@ -851,10 +1013,10 @@ eagle_sweep_kernel(
   // hands it back. With iterations == 0 nothing changed (and no barrier
   // orders this store after the other workgroups' prologue loads).
   if (resident && blockIdx.x == 0 && iterations > 0) {
-    for (int e = tid; e < pool_elems; e += BLOCK) {
+    for (int e = wt; e < pool_elems; e += BLOCK) {
       cstore(pool_cont + e, st_pool[e]);
     }
-    for (int p = tid; p < pool_size; p += BLOCK) {
+    for (int p = wt; p < pool_size; p += BLOCK) {
       cstore(rewards + p, st_rewards[p]);
       cstore(perturbations + p, st_perts[p]);
     }
@@ -895,7 +1057,7 @@ extern "C" int launch_eagle_sweep(
                               hipDeviceAttributeMultiprocessorCount, dev);
   int blocks_per_cu = 0;
   hipError_t err = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &blocks_per_cu, (const void*)eagle_sweep_kernel, BLOCK, 0);
+      &blocks_per_cu, (const void*)eagle_sweep_kernel, SWEEP_THREADS, 0);
   if (err != hipSuccess || blocks_per_cu < 1) return 0;
   const int tiles_n = (n + VZ_QF_TILE - 1) / VZ_QF_TILE;
   // Grid size is a pure throughput knob (every phase is a grid-stride
@@ -908,7 +1070,12 @@ extern "C" int launch_eagle_sweep(
   // the grid tables in profiles/bench_sweep_two_barriers.md and
   // profiles/bench_sweep_loads_in_flight.md. Raising the cap is left to
   // a change of its own, A/B'd over the other shapes;
-  // tests/test_sweep_kernel.py asserts 128. The floor: tiles_n^2
+  // tests/test_sweep_kernel.py asserts 128. The grid counts workgroups
+  // of SWEEP_THREADS = 512 threads: each runs two tiles of phase B at
+  // once, one per half, so 128 workgroups hold the 256 tiles of the
+  // headline shape in one trip with 128 arrivals at the barrier
+  // (profiles/bench_sweep_two_tiles.md). The occupancy query and the
+  // launch both use 512 threads. The floor: tiles_n^2
   // starves phase A at small N (4 WGs at N=125 ran at 107 us/iter).
   // Override with VIZIER_AMD_SWEEP_GRID.
   int grid = tiles_n * tiles_n;                   // fills phase B
@@ -934,7 +1101,7 @@ extern "C" int launch_eagle_sweep(
       &seed_update, &amp2, &mean_c, &acq, &coef, &best_value,
       &tr_radius};
   err = hipLaunchCooperativeKernel((const void*)eagle_sweep_kernel,
-                                   dim3(grid), dim3(BLOCK), args, 0,
+                                   dim3(grid), dim3(SWEEP_THREADS), args, 0,
                                    stream);
   if (err != hipSuccess) return -(int)err;
   return grid;

@@ -105,8 +105,9 @@ def test_default_is_v6(ext):
   want, want_info = potrf(ext, K, 'v6')
   assert torch.equal(torch.tril(L).cpu(), want)
   assert torch.equal(info.cpu(), want_info)
-  with pytest.raises(RuntimeError, match='impl must be one of'):
-    ext.batched_potrf(K.cuda(), 'v7')
+  for retired in ('v3', 'v4', 'v5', 'v7'):
+    with pytest.raises(RuntimeError, match='impl must be one of'):
+      ext.batched_potrf(K.cuda(), retired)
 
 
 @pytest.mark.parametrize('pivot', [-1.0, float('nan')])

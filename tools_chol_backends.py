@@ -1,8 +1,9 @@
 """Times batched fp32 Cholesky backends at the fit shapes.
 
-Compares: custom v2 (multi-launch), custom v3 (cooperative, opt-in via
-env), torch-MAGMA, torch-hipSOLVER — at (R=3, N=1000) grad-eval and
-(R=12, N=1000) line-search-ladder shapes. Each backend in-process
+Compares: the custom default (v6, or what VIZIER_AMD_CHOL_IMPL names),
+torch-MAGMA, torch-hipSOLVER — at (R=3, N=1000) grad-eval and
+(R=12, N=1000) line-search-ladder shapes; `impl [v2 v6]` times the custom
+implementations against each other. Each backend in-process
 except the preferred_linalg_library switch (process-global, so run
 MAGMA first, then hipSOLVER via a subprocess if needed).
 """
@@ -52,7 +53,7 @@ for r, n in ((3, 1000), (12, 1000), (3, 2000)):
   k = make_k(r, n)
   if which in ('all', 'custom'):
     ms = bench(lambda: ext.batched_potrf(k))
-    print(f'R={r:3d} N={n}: custom_v2      {ms:8.3f} ms', flush=True)
+    print(f'R={r:3d} N={n}: custom_default {ms:8.3f} ms', flush=True)
   if which in ('all', 'magma'):
     torch.backends.cuda.preferred_linalg_library('magma')
     ms = bench(lambda: torch.linalg.cholesky_ex(k))

@@ -136,13 +136,6 @@ extern "C" void batched_potrf_launch_shape(int n, int impl, int out[2]);
 extern "C" void launch_batched_potrf(float* A, int* info, float* dscratch,
                                      int r, int n, int impl,
                                      hipStream_t stream);
-extern "C" int launch_batched_potrf_coop(float* A, int* info,
-                                         unsigned int* bar, int r, int n,
-                                         hipStream_t stream);
-extern "C" int launch_batched_potrf_v5(const float* A, float* panels,
-                                       float* dscratch, float* L,
-                                       int* info, unsigned int* bar,
-                                       int r, int n, hipStream_t stream);
 extern "C" void launch_batched_trsv_lower(const float* L, float* b,
                                           int r, int n, int variant,
                                           hipStream_t stream);
@@ -1139,10 +1132,9 @@ torch::Tensor hv_scalarize_tr(
   return out;
 }
 
-// Implementation ladder. `impl` is "v2" .. "v6"; "" means
-// VIZIER_AMD_CHOL_IMPL, read once per process, and v6 when that is unset.
-// v2 and v6 factor the same bits (tests/test_potrf_tiled.py). Timings at
-// N = 1000:
+// `impl` is "v2" or "v6"; "" means VIZIER_AMD_CHOL_IMPL, read once per
+// process, and v6 when that is unset or names neither. v2 and v6 factor
+// the same bits (tests/test_potrf_tiled.py). Timings at N = 1000:
 //   v6 (default): v2's two launches per 32-column round, trailing update
 //       on 64 x 64 tiles and a column-wise panel solve: 0.53 / 0.63 /
 //       0.71 ms at R = 2 / 8 / 16 (profiles/bench_potrf_tiled.md).
@@ -1153,23 +1145,16 @@ torch::Tensor hv_scalarize_tr(
 //       workgroup walks every row below it, and each panel row is a
 //       528-step dependent chain. v6 runs the same rounds with the same
 //       kernel boundaries in under a quarter of the time.
-//   v5: persistent left-looking cooperative kernel (read-only input
-//       stays cached, panel-major once-written output, diagonal via
-//       agent-scope scratch), 3.15 ms: ~500 barrier-separated LDS staging
-//       steps at occupancy 2.
-//   v3: right-looking cooperative, 2x slower than v2 (the trailing matrix
-//       is cross-workgroup mutable, so all its traffic is memory-side).
-//   v4: fused one-kernel-per-round with recompute, occupancy 1
-//       (VGPR 256 + 248 AGPRs), 3.63 ms.
+// DESIGN.md describes the retired designs (v1, v3, v4, v5) and what they
+// measured.
 int resolve_potrf_impl(const std::string& impl) {
   const auto parse = [](const std::string& s) {
-    return s.size() == 2 && s[0] == 'v' && s[1] >= '2' && s[1] <= '6'
-        ? s[1] - '0' : 0;
+    return s == "v2" ? 2 : s == "v6" ? 6 : 0;
   };
   if (!impl.empty()) {
     const int version = parse(impl);
-    TORCH_CHECK(version != 0, "batched_potrf impl must be one of v2, v3, "
-                "v4, v5, v6, got '", impl, "'");
+    TORCH_CHECK(version != 0, "batched_potrf impl must be one of v2, v6, "
+                "got '", impl, "'");
     return version;
   }
   static const int from_env = [&]() {
@@ -1187,8 +1172,6 @@ int resolve_potrf_impl(const std::string& impl) {
 std::vector<int64_t> batched_potrf_launch_shape_py(int64_t n,
                                                    const std::string& impl) {
   const int version = resolve_potrf_impl(impl);
-  TORCH_CHECK(version == 2 || version == 6,
-              "launch shape is defined for v2 and v6 only");
   TORCH_CHECK(n >= 1, "n must be >= 1");
   int out[2];
   batched_potrf_launch_shape((int)n, version, out);
@@ -1212,43 +1195,17 @@ std::vector<torch::Tensor> batched_potrf(torch::Tensor K,
   const int r = K.size(0), n = K.size(1);
   const int impl = resolve_potrf_impl(impl_name);
   auto info = torch::zeros({r}, K.options().dtype(torch::kInt32));
-  if (impl == 5) {
-    auto L = torch::empty_like(K);
-    const long pk = (n + 31) / 32;
-    auto panels = torch::empty({(long)r * pk * n * 32}, K.options());
-    auto dscratch = torch::empty({(long)r * 32 * 32}, K.options());
-    auto bar = torch::zeros({2}, K.options().dtype(torch::kInt32));
-    if (launch_batched_potrf_v5(
-            K.data_ptr<float>(), panels.data_ptr<float>(),
-            dscratch.data_ptr<float>(), L.data_ptr<float>(),
-            info.data_ptr<int>(),
-            reinterpret_cast<unsigned int*>(bar.data_ptr<int>()),
-            r, n, current_stream()) == 0) {
-      return {L, info};
-    }
-  }
   auto L = K.clone();
-  if (impl == 3) {
-    auto bar = torch::zeros({2}, K.options().dtype(torch::kInt32));
-    if (launch_batched_potrf_coop(
-            L.data_ptr<float>(), info.data_ptr<int>(),
-            reinterpret_cast<unsigned int*>(bar.data_ptr<int>()),
-            r, n, current_stream()) == 0) {
-      return {L, info};
-    }
-  }
-  // v3 / v5 fall back to v2 when their cooperative launch is refused.
-  const int launcher = impl == 6 || impl == 4 ? impl : 2;
   // Rounds with more than one row tile park their factored diagonal
   // block here instead of overwriting what the other tiles still read.
   torch::Tensor dscratch;
   float* dscratch_p = nullptr;
-  if (batched_potrf_needs_scratch(n, launcher)) {
+  if (batched_potrf_needs_scratch(n, impl)) {
     dscratch = torch::empty({r, 32, 32}, K.options());
     dscratch_p = dscratch.data_ptr<float>();
   }
   launch_batched_potrf(L.data_ptr<float>(), info.data_ptr<int>(),
-                       dscratch_p, r, n, launcher, current_stream());
+                       dscratch_p, r, n, impl, current_stream());
   return {L, info};
 }
 
@@ -1711,7 +1668,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "triangle of L is defined; the strict upper triangle holds "
         "unspecified values. info[r] is the 1-based first column whose "
         "pivot is not > 0 (zero, negative or NaN), 0 on success. impl = "
-        "v2 .. v6; '' = VIZIER_AMD_CHOL_IMPL, else v6 (gfx950)",
+        "v2 | v6; '' = VIZIER_AMD_CHOL_IMPL, else v6 (gfx950)",
         py::arg("K"), py::arg("impl") = "");
   m.def("batched_potrf_launch_shape", &batched_potrf_launch_shape_py,
         "(rows per panel workgroup, panel row tiles of round 0, trailing "

@@ -132,7 +132,9 @@
 // correct: grids of 1, 7 and 200 workgroups are run by
 // tests/test_sweep_kernel.py); the launcher clamps the grid to the
 // cooperative occupancy limit, and cooperative launch guarantees
-// co-residency.
+// co-residency. Where the device's one cooperative queue belongs to
+// another process, the launcher launches the same grid ordinarily (see
+// launch_eagle_sweep).
 
 #include <hip/hip_runtime.h>
 
@@ -1103,6 +1105,26 @@ extern "C" int launch_eagle_sweep(
   err = hipLaunchCooperativeKernel((const void*)eagle_sweep_kernel,
                                    dim3(grid), dim3(SWEEP_THREADS), args, 0,
                                    stream);
+  if (err == hipErrorIllegalState) {
+    // The runtime found no cooperative queue for this process, and nothing
+    // was enqueued. A device can have a single such queue, which a process
+    // keeps from its first cooperative launch until it exits (a
+    // virtualised GPU; a parent process that ran a sweep before it started
+    // this one). The kernel asks only co-residency of a cooperative
+    // launch: grid_sync is its own barrier, on a counter in global memory.
+    // An ordinary launch of the same grid, already clamped to what the
+    // device holds at once, becomes co-resident as soon as the kernels
+    // that were running ahead of it drain; a workgroup that waits in
+    // grid_sync keeps its slot and takes nobody else's. What it cannot
+    // exclude is a second barrier kernel launched the same way that
+    // shares the device and, with this one, does not fit: the default
+    // grid of at most 128 workgroups is half of max_grid on an MI355X
+    // (one workgroup per CU, 256 CUs). Every other error is returned as
+    // before.
+    (void)hipGetLastError();  // handled here: leave none for a later check
+    err = hipLaunchKernel((const void*)eagle_sweep_kernel, dim3(grid),
+                          dim3(SWEEP_THREADS), args, 0, stream);
+  }
   if (err != hipSuccess) return -(int)err;
   return grid;
 }

@@ -579,6 +579,9 @@ class VizierGPBandit(Designer, Predictor):
     # sweep in the persistent cooperative megakernel (continuous-only).
     score_fn.scoring = scoring
     score_fn.codec_identity = self._codec.identity
+    # The mixed-space megakernel builds the dense candidate itself, from
+    # the codec's column maps.
+    score_fn.codec = self._codec
     return score_fn, 1
 
   def _qei_hip_score_fn(self, posterior, eps: torch.Tensor,

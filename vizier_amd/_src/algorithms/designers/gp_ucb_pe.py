@@ -114,6 +114,7 @@ class VizierGPUCBPEBandit(Designer):
     self._mt_raw = None           # joint multitask warm start
     self._last_fit_count = -1
     self._last_suggest_completed = 0
+    self._last_optimizer = None      # the most recent UCB / PE sweep's
     self._last_set_optimizer = None  # the most recent set-PE sweep's
     from vizier_amd._src.algorithms.designers.quasi_random import (
         QuasiRandomDesigner,
@@ -492,6 +493,9 @@ class VizierGPUCBPEBandit(Designer):
         categorical_sizes=self._codec.categorical_sizes,
         seed=self._seed + len(self._completed) + x_all.shape[0],
         device=self._device, dtype=cfg.dtype)
+    # Kept for diagnostics, as GP-Bandit keeps its own: last_used_graph /
+    # last_used_megakernel of the most recent single-point sweep.
+    self._last_optimizer = optimizer
 
     if self._mo_posteriors is not None:
       # Eagle prior seeding needs scalar rewards: use the scalarized
@@ -653,6 +657,9 @@ class VizierGPUCBPEBandit(Designer):
         # sequential-suggest case; same fast path as GP-Bandit).
         score_fn.scoring = scoring
         score_fn.codec_identity = self._codec.identity
+        # The mixed-space megakernel builds the dense candidate itself, from
+        # the codec's column maps.
+        score_fn.codec = self._codec
       else:
         # Pending points anchor the trust region elsewhere: composed
         # rocBLAS path, not capturable on this ROCm build.

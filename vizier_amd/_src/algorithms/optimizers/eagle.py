@@ -146,8 +146,10 @@ class VectorizedEagleStrategy:
       self._ext = ops.require_ext()
       # [0:2] device iteration counters; [2:10] megakernel per-phase
       # cycle accumulators (A, barA, B, barB, B2, barB2, C, barC) —
-      # written by workgroup 0 of eagle_sweep for profiling.
-      self._iter_t = torch.zeros(12, dtype=torch.long,
+      # written by workgroup 0 of eagle_sweep for profiling; [10:12]
+      # phase B's stage / main, [12] the categorical mutation of
+      # eagle_sweep_mixed.
+      self._iter_t = torch.zeros(14, dtype=torch.long,
                                  device=self.device)
       self._out_cont = torch.empty(self.batch_size, n_parallel,
                                    n_continuous, dtype=dtype,
@@ -156,9 +158,30 @@ class VectorizedEagleStrategy:
                                   self.n_categorical, dtype=torch.long,
                                   device=self.device)
       self._max_cat_host = max(self.categorical_sizes, default=0)
+      self._mixed_maps = None
     else:
       self._ext = None
       self._iter_t = None
+
+  def categorical_factor(self) -> float:
+    """The perturbation factor of the categorical mutation."""
+    cfg = self.config
+    return (cfg.pure_categorical_perturbation_factor
+            if self.n_continuous == 0
+            else cfg.categorical_perturbation_factor)
+
+  def mixed_sweep_maps(self, codec):
+    """int32 device tensors (cat_sizes, cont_cols, cat_start) that
+    `eagle_sweep_mixed` takes: the codec's column maps, built once per
+    strategy."""
+    if self._mixed_maps is None:
+      def i32(values):
+        return torch.tensor(list(values), dtype=torch.int32,
+                            device=self.device)
+      self._mixed_maps = (
+          i32(self.categorical_sizes), i32(codec.continuous_cols),
+          i32(start for start, _ in codec.onehot_specs))
+    return self._mixed_maps
 
   # -- random sampling ------------------------------------------------------
 
@@ -269,9 +292,7 @@ class VectorizedEagleStrategy:
       self._iter_t[:2].fill_(state.iterations)
     if self._ext is not None:
       cfg = self.config
-      cat_factor = (cfg.pure_categorical_perturbation_factor
-                    if self.n_continuous == 0
-                    else cfg.categorical_perturbation_factor)
+      cat_factor = self.categorical_factor()
       suggest_kernel = (self._ext.eagle_suggest_f64 if self._f64_hip
                         else self._ext.eagle_suggest)
       out_cont, out_cat = suggest_kernel(

@@ -121,7 +121,8 @@ class VectorizedOptimizer:
     """Persistent-megakernel preconditions: GPU ext, continuous-only
     with at most 512 features (the kernel's xq_lds), q == 1, and a
     fused-able ScoringFunction (same conditions as the chunked HIP
-    scorer fast path)."""
+    scorer fast path). A space with categorical parameters (non-identity
+    codec) is answered by _megakernel_mixed_applicable."""
     import os
     if os.environ.get('VIZIER_AMD_MEGAKERNEL', '1') != '1':
       # Default ON: 68 us/iteration vs 85 for the hipGraph replay
@@ -134,9 +135,10 @@ class VectorizedOptimizer:
       return False
     strategy = self.strategy
     scoring = getattr(score_fn, 'scoring', None)
-    if (strategy._ext is None or scoring is None or
-        not getattr(score_fn, 'codec_identity', False)):
+    if strategy._ext is None or scoring is None:
       return False
+    if not getattr(score_fn, 'codec_identity', False):
+      return self._megakernel_mixed_applicable(score_fn)
     if strategy.categorical_sizes or strategy.n_parallel != 1:
       return False
     if strategy.dtype != torch.float32:
@@ -152,6 +154,45 @@ class VectorizedOptimizer:
             # The kernel's dc is x's width (continuous-only, identity
             # codec: strategy.n_continuous); xq_lds holds 512.
             and post.x.shape[1] <= 512)
+
+  # eagle_sweep_common.h: floats of the continuous pool, and entries of the
+  # categorical pool, that a workgroup of the mixed kernel keeps in LDS.
+  _RESIDENT_CAP = 4096
+  _RESIDENT_CAT_CAP = 3072
+
+  def _megakernel_mixed_applicable(self, score_fn: ScoreFn) -> bool:
+    """Preconditions of the mixed-space megakernel (eagle_sweep_mixed.hip)
+    for a non-identity codec: at least one categorical parameter, q == 1,
+    fp32, the fused scorer with an anchored trust region, both halves of
+    the pool within the resident caps, and N < 4096. Below N = 4096 the
+    standalone scorer takes the same tile quadform, so the suggestions are
+    bit-identical to the hipGraph path's; from 4096 up the two agree to
+    tolerance only, and that range stays on the hipGraph path.
+    VIZIER_AMD_MEGAKERNEL_MIXED=0 forces the hipGraph path for mixed
+    spaces only."""
+    import os
+    if os.environ.get('VIZIER_AMD_MEGAKERNEL_MIXED', '1') != '1':
+      return False
+    strategy = self.strategy
+    scoring = score_fn.scoring
+    codec = getattr(score_fn, 'codec', None)
+    if (codec is None or not strategy.categorical_sizes or
+        strategy.n_parallel != 1 or strategy.dtype != torch.float32):
+      return False
+    post = scoring.posterior
+    pool = strategy.pool_size
+    return (scoring._acq_name is not None and scoring._tr_anchored and
+            getattr(scoring, 'gram_dtype', 'fp32') == 'fp32' and
+            post.K_inv is not None and post.x.is_cuda and
+            pool <= 128 and strategy.batch_size <= 32 and
+            pool % strategy.batch_size == 0 and
+            pool * strategy.n_continuous <= self._RESIDENT_CAP and
+            pool * strategy.n_categorical <= self._RESIDENT_CAT_CAP and
+            post.x.shape[1] <= 512 and
+            post.x.shape[1] == codec.n_total and
+            codec.n_continuous == strategy.n_continuous and
+            list(codec.categorical_sizes) == strategy.categorical_sizes and
+            post.x.shape[0] < 4096)
 
   def _optimize_megakernel(self, score_fn: ScoreFn, count: int, state,
                            iterations: int) -> VectorizedStrategyResults:
@@ -201,18 +242,39 @@ class VectorizedOptimizer:
       amp2 = scoring._amp * scoring._amp
       tr_radius = (scoring._tr_radius
                    if scoring.trust_region is not None else 0.0)
-      strategy._ext.eagle_sweep(
-          state.continuous, state.rewards, state.perturbations,
-          state.best_reward.reshape(1), strategy._iter_t, barrier_buf,
-          post.x, inv_ls, post.alpha, post.K_inv,
-          strategy._out_cont, k_ws, mu_ws, dist_ws, var_ws,
+      common = (
           n_batches, b, strategy.pool_size, state.iterations, remaining,
           cfg.visibility, cfg.gravity, cfg.negative_gravity,
-          cfg.normalization_scale, cfg.penalize_factor,
-          cfg.perturbation_lower_bound, cfg.perturbation,
-          strategy._seed, strategy._seed ^ 0xABCDEF, amp2,
+          cfg.normalization_scale)
+      tail = (
+          cfg.penalize_factor, cfg.perturbation_lower_bound,
+          cfg.perturbation, strategy._seed, strategy._seed ^ 0xABCDEF, amp2,
           scoring._mean_c, ops.ACQ_CODES[scoring._acq_name],
           scoring._coef, scoring._best, tr_radius)
+      if strategy.categorical_sizes:
+        # Mixed space: the kernel carries the categorical half of the
+        # state and assembles the dense candidate from the codec's maps.
+        cat_sizes, cont_cols, cat_start = strategy.mixed_sweep_maps(
+            score_fn.codec)
+        tr_mask = scoring._onehot_u8
+        if tr_mask is None:
+          tr_mask = _torch.zeros(post.x.shape[1], dtype=_torch.uint8,
+                                 device=dev)
+        strategy._ext.eagle_sweep_mixed(
+            state.continuous, state.categorical, state.rewards,
+            state.perturbations, state.best_reward.reshape(1),
+            strategy._iter_t, barrier_buf, post.x, inv_ls, post.alpha,
+            post.K_inv, cat_sizes, cont_cols, cat_start, tr_mask,
+            strategy._out_cont, strategy._out_cat, k_ws, mu_ws, dist_ws,
+            var_ws, *common, strategy.categorical_factor(),
+            cfg.prob_same_category_without_perturbation, *tail)
+      else:
+        strategy._ext.eagle_sweep(
+            state.continuous, state.rewards, state.perturbations,
+            state.best_reward.reshape(1), strategy._iter_t, barrier_buf,
+            post.x, inv_ls, post.alpha, post.K_inv,
+            strategy._out_cont, k_ws, mu_ws, dist_ws, var_ws,
+            *common, *tail)
       state.iterations += remaining
 
     rewards = torch.where(torch.isfinite(state.rewards), state.rewards,

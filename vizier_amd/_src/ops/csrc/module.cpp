@@ -164,6 +164,23 @@ extern "C" int launch_eagle_sweep(
     float amp2, float mean_c, int acq, float coef, float best_value,
     float tr_radius, hipStream_t stream);
 
+extern "C" int launch_eagle_sweep_mixed(
+    float* pool_cont, long long* pool_cat, float* rewards,
+    float* perturbations, float* best_reward, unsigned long long* iter_ptr,
+    unsigned int* barrier_buf, const float* x, const float* inv_ls,
+    const float* alpha, const float* kinv, const int* cat_sizes,
+    const int* cont_cols, const int* cat_start,
+    const unsigned char* tr_mask, float* out_cont, long long* out_cat,
+    float* k_ws, float* mu_ws, float* dist_ws, float* var_ws,
+    float* slot_ws, int* slot_cat, int n_batches, int batch_size,
+    int pool_size, int dc, int dcat, int d, int max_cat, int n,
+    long long it_start, long long iterations, float visibility,
+    float gravity, float neg_gravity, float norm_scale, float cat_factor,
+    float p_same, float penalize_factor, float perturbation_lower_bound,
+    float base_perturbation, unsigned long long seed_suggest,
+    unsigned long long seed_update, float amp2, float mean_c, int acq,
+    float coef, float best_value, float tr_radius, hipStream_t stream);
+
 extern "C" void launch_eagle_update(
     float* pool_cont, long* pool_cat, float* rewards, float* perturbations,
     const float* batch_cont, const long* batch_cat,
@@ -1543,6 +1560,194 @@ int64_t eagle_sweep(
   return ret;
 }
 
+// The mixed-space sweep (eagle_sweep_mixed.hip). cat_sizes, cont_cols and
+// cat_start are int32 device tensors; they are copied to the host once
+// here, outside the sweep, to check that the two column maps tile the D
+// dense columns exactly.
+int64_t eagle_sweep_mixed(
+    torch::Tensor pool_cont, torch::Tensor pool_cat, torch::Tensor rewards,
+    torch::Tensor perturbations, torch::Tensor best_reward,
+    torch::Tensor iter_counter, torch::Tensor barrier_buf, torch::Tensor x,
+    torch::Tensor inv_ls, torch::Tensor alpha, torch::Tensor kinv,
+    torch::Tensor cat_sizes, torch::Tensor cont_cols,
+    torch::Tensor cat_start, torch::Tensor tr_mask, torch::Tensor out_cont,
+    torch::Tensor out_cat, torch::Tensor k_ws, torch::Tensor mu_ws,
+    torch::Tensor dist_ws, torch::Tensor var_ws, int64_t n_batches,
+    int64_t batch_size, int64_t pool_size, int64_t it_start,
+    int64_t iterations, double visibility, double gravity,
+    double neg_gravity, double norm_scale, double cat_factor, double p_same,
+    double penalize_factor, double perturbation_lower_bound,
+    double base_perturbation, int64_t seed_suggest, int64_t seed_update,
+    double amp2, double mean_c, int64_t acq, double coef, double best_value,
+    double tr_radius) {
+  // Every check throws before anything is launched; the state and the
+  // workspaces are written in place and never copied.
+  check_inplace(pool_cont, torch::kFloat32, "pool_cont");
+  check_inplace(pool_cat, torch::kInt64, "pool_cat");
+  check_inplace(rewards, torch::kFloat32, "rewards");
+  check_inplace(perturbations, torch::kFloat32, "perturbations");
+  check_inplace(best_reward, torch::kFloat32, "best_reward");
+  check_inplace(iter_counter, torch::kInt64, "iter_counter");
+  check_inplace(barrier_buf, torch::kInt32, "barrier_buf");
+  check_inplace(out_cont, torch::kFloat32, "out_cont");
+  check_inplace(out_cat, torch::kInt64, "out_cat");
+  check_inplace(k_ws, torch::kFloat32, "k_ws");
+  check_inplace(mu_ws, torch::kFloat32, "mu_ws");
+  check_inplace(dist_ws, torch::kFloat32, "dist_ws");
+  check_inplace(var_ws, torch::kFloat32, "var_ws");
+  x = check_f32(x, "x");
+  inv_ls = check_f32(inv_ls, "inv_ls");
+  alpha = check_f32(alpha, "alpha");
+  kinv = check_f32(kinv, "kinv");
+  for (const torch::Tensor* t : {&cat_sizes, &cont_cols, &cat_start}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt32 &&
+                t->dim() == 1,
+                "cat_sizes / cont_cols / cat_start must be 1-D int32 GPU "
+                "tensors");
+  }
+  cat_sizes = cat_sizes.contiguous();
+  cont_cols = cont_cols.contiguous();
+  cat_start = cat_start.contiguous();
+  TORCH_CHECK(tr_mask.is_cuda() && tr_mask.scalar_type() == torch::kUInt8,
+              "tr_mask must be a uint8 GPU tensor");
+  tr_mask = tr_mask.contiguous();
+  TORCH_CHECK(barrier_buf.numel() >= 2, "barrier_buf must be int32 (2,)");
+  TORCH_CHECK(x.dim() == 2, "x must be (N, D)");
+  const int64_t d64 = x.size(1), n64 = x.size(0);
+  const int64_t dc64 = cont_cols.numel(), dcat64 = cat_sizes.numel();
+  // xq_lds[512] holds the dense candidate; a pair and a parameter table
+  // entry exist per one-hot column.
+  TORCH_CHECK(d64 >= 1 && d64 <= 512,
+              "eagle_sweep_mixed supports 1 <= D <= 512, got ", d64);
+  TORCH_CHECK(dc64 >= 0 && dc64 <= d64,
+              "eagle_sweep_mixed needs 0 <= Dc <= D, got ", dc64);
+  TORCH_CHECK(dcat64 >= 1,
+              "eagle_sweep_mixed needs Dcat >= 1 (continuous spaces run "
+              "eagle_sweep)");
+  TORCH_CHECK(cat_start.numel() == dcat64,
+              "cat_start must have Dcat = ", dcat64, " elements");
+  TORCH_CHECK(n64 >= 1 && n64 <= 8192,
+              "eagle_sweep_mixed supports 1 <= N <= 8192, got ", n64);
+  TORCH_CHECK(pool_size >= 1 && pool_size <= 128,
+              "eagle_sweep_mixed supports 1 <= pool <= 128, got ",
+              pool_size);
+  TORCH_CHECK(batch_size >= 1 && batch_size <= 32,
+              "eagle_sweep_mixed supports 1 <= batch <= 32, got ",
+              batch_size);
+  TORCH_CHECK(n_batches >= 1 && n_batches * batch_size == pool_size,
+              "pool_size must be n_batches * batch_size, got ", pool_size,
+              " != ", n_batches, " * ", batch_size);
+  TORCH_CHECK(iterations >= 0, "iterations must be >= 0, got ", iterations);
+  // Resident mode only: RESIDENT_CAP and RESIDENT_CAT_CAP of
+  // eagle_sweep_common.h.
+  TORCH_CHECK(pool_size * dc64 <= 4096,
+              "eagle_sweep_mixed keeps the pool in LDS: pool * Dc <= 4096, "
+              "got ", pool_size * dc64);
+  TORCH_CHECK(pool_size * dcat64 <= 3072,
+              "eagle_sweep_mixed keeps the categorical pool in LDS: "
+              "pool * Dcat <= 3072, got ", pool_size * dcat64);
+  // The column maps, on the host: every size >= 1, every column in range,
+  // and the continuous columns and one-hot blocks cover 0 .. D - 1 once.
+  const torch::Tensor sizes_h = cat_sizes.cpu(), cols_h = cont_cols.cpu(),
+                      start_h = cat_start.cpu();
+  const int* sizes_p = sizes_h.data_ptr<int>();
+  const int* cols_p = cols_h.data_ptr<int>();
+  const int* start_p = start_h.data_ptr<int>();
+  std::vector<char> used((size_t)d64, 0);
+  int64_t sum_sizes = 0;
+  int max_cat = 0;
+  for (int64_t j = 0; j < dcat64; ++j) {
+    TORCH_CHECK(sizes_p[j] >= 1, "cat_sizes[", j, "] must be >= 1, got ",
+                sizes_p[j]);
+    sum_sizes += sizes_p[j];
+    max_cat = std::max(max_cat, sizes_p[j]);
+  }
+  TORCH_CHECK(dc64 + sum_sizes == d64, "Dc + sum(cat_sizes) must be D: ",
+              dc64, " + ", sum_sizes, " != ", d64);
+  for (int64_t i = 0; i < dc64; ++i) {
+    TORCH_CHECK(cols_p[i] >= 0 && cols_p[i] < d64 && !used[cols_p[i]],
+                "cont_cols[", i, "] = ", cols_p[i],
+                " is out of range or taken twice");
+    used[cols_p[i]] = 1;
+  }
+  for (int64_t j = 0; j < dcat64; ++j) {
+    TORCH_CHECK(start_p[j] >= 0 && start_p[j] + sizes_p[j] <= d64,
+                "one-hot block ", j, " leaves the D columns");
+    for (int c = 0; c < sizes_p[j]; ++c) {
+      TORCH_CHECK(!used[start_p[j] + c], "one-hot block ", j,
+                  " overlaps another column");
+      used[start_p[j] + c] = 1;
+    }
+  }
+  const int d = (int)d64, dc = (int)dc64, dcat = (int)dcat64, n = (int)n64;
+  TORCH_CHECK(pool_cont.numel() == pool_size * dc &&
+              pool_cat.numel() == pool_size * dcat,
+              "pool_cont / pool_cat must be (pool, Dc) / (pool, Dcat), q=1");
+  TORCH_CHECK(rewards.numel() == pool_size &&
+              perturbations.numel() == pool_size,
+              "rewards / perturbations must have pool_size = ", pool_size,
+              " elements");
+  TORCH_CHECK(best_reward.numel() >= 1, "best_reward must not be empty");
+  // [0:2] iteration counters, [2:12] the per-phase cycle accumulators,
+  // [12] the categorical mutation's.
+  TORCH_CHECK(iter_counter.numel() >= 14,
+              "iter_counter must have >= 14 slots, got ",
+              iter_counter.numel());
+  TORCH_CHECK(inv_ls.numel() == d, "inv_ls must have ", d,
+              " elements, got ", inv_ls.numel());
+  TORCH_CHECK(tr_mask.numel() == d, "tr_mask must have ", d,
+              " elements, got ", tr_mask.numel());
+  TORCH_CHECK(alpha.numel() == n, "alpha must have ", n, " elements, got ",
+              alpha.numel());
+  TORCH_CHECK(kinv.dim() == 2 && kinv.size(0) == n && kinv.size(1) == n,
+              "kinv must be (", n, ", ", n, ")");
+  TORCH_CHECK(out_cont.numel() >= batch_size * dc,
+              "out_cont must hold batch * Dc elements");
+  TORCH_CHECK(out_cat.numel() >= batch_size * dcat,
+              "out_cat must hold batch * Dcat elements");
+  TORCH_CHECK(k_ws.numel() >= batch_size * n,
+              "k_ws must hold batch * N elements");
+  TORCH_CHECK(mu_ws.numel() >= batch_size && dist_ws.numel() >= batch_size,
+              "mu_ws / dist_ws must hold batch elements");
+  const long tiles_n = (n + 63) / 64;
+  TORCH_CHECK(var_ws.numel() >= batch_size * (tiles_n * tiles_n + 1),
+              "var_ws must be (B, tiles^2 + 1)");
+  // The parity slots (see eagle_sweep.hip): candidates, mu and dist as
+  // floats, the categorical choice as int32.
+  torch::Tensor slot_ws = torch::empty(
+      {2, batch_size * (dc64 + 2)},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  torch::Tensor slot_cat = torch::empty(
+      {2, batch_size * dcat64},
+      torch::TensorOptions().dtype(torch::kInt32).device(x.device()));
+  const int ret = launch_eagle_sweep_mixed(
+      dc ? pool_cont.data_ptr<float>() : nullptr,
+      (long long*)pool_cat.data_ptr<int64_t>(), rewards.data_ptr<float>(),
+      perturbations.data_ptr<float>(), best_reward.data_ptr<float>(),
+      (unsigned long long*)iter_counter.data_ptr<int64_t>(),
+      (unsigned int*)barrier_buf.data_ptr<int>(), x.data_ptr<float>(),
+      inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
+      kinv.data_ptr<float>(), cat_sizes.data_ptr<int>(),
+      dc ? cont_cols.data_ptr<int>() : nullptr, cat_start.data_ptr<int>(),
+      tr_mask.data_ptr<unsigned char>(),
+      dc ? out_cont.data_ptr<float>() : nullptr,
+      (long long*)out_cat.data_ptr<int64_t>(), k_ws.data_ptr<float>(),
+      mu_ws.data_ptr<float>(), dist_ws.data_ptr<float>(),
+      var_ws.data_ptr<float>(), slot_ws.data_ptr<float>(),
+      slot_cat.data_ptr<int>(), (int)n_batches, (int)batch_size,
+      (int)pool_size, dc, dcat, d, max_cat, n, (long long)it_start,
+      (long long)iterations, (float)visibility, (float)gravity,
+      (float)neg_gravity, (float)norm_scale, (float)cat_factor,
+      (float)p_same, (float)penalize_factor,
+      (float)perturbation_lower_bound, (float)base_perturbation,
+      (unsigned long long)seed_suggest, (unsigned long long)seed_update,
+      (float)amp2, (float)mean_c, (int)acq, (float)coef, (float)best_value,
+      (float)tr_radius, current_stream());
+  TORCH_CHECK(ret > 0, "cooperative eagle_sweep_mixed launch failed (code ",
+              ret, ")");
+  return ret;
+}
+
 // -- fp64 parity-mode bindings -------------------------------------------------
 
 // Runs the three fp64 scorer kernels on the current stream. `want_score`
@@ -1714,4 +1919,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("eagle_update", eagle_update, "Fused Eagle update step (gfx950)");
   m.def("eagle_sweep", &eagle_sweep,
         "Persistent cooperative Eagle sweep megakernel (gfx950)");
+  m.def("eagle_sweep_mixed", &eagle_sweep_mixed,
+        "Persistent Eagle sweep megakernel for mixed categorical + "
+        "continuous spaces, pool resident in LDS (gfx950)");
 }

@@ -92,6 +92,16 @@ class GPBanditConfig:
   # _linear_coef; tuned_gp_models.py:204): None disables it. Posteriors
   # with a linear term score via the composed predict path.
   linear_coef: Optional[float] = None
+  # Single-point scorer of a linear_coef posterior: 'torch' (default: the
+  # predict path, eager sweep) or 'hip' (opt-in: the fit also caches the
+  # combined kernel's inverse and the sweep scores through the fused
+  # posterior_score_linear.hip scorer, captured in a hipGraph). 'hip'
+  # applies on the GPU in float32 with UCB / EI / PI and a trust region
+  # anchored at the training points; anything else, and the qEI set
+  # scorer, keeps the torch path. The variance then comes from a K^-1
+  # quadform instead of a triangular solve and the captured sweep selects
+  # from the final pool, so suggestions can differ from 'torch'.
+  linear_scorer: str = 'torch'
   # Multi-metric surrogate: 'independent' (default, one GP per metric)
   # or 'separable'/'separable_diag' joint task kernels
   # (gp_bandit.py:157 _multitask_type; multitask_tuned_gp_models.py:41).
@@ -120,6 +130,9 @@ class VizierGPBandit(Designer, Predictor):
     if self._config.qei_scorer not in ('torch', 'hip'):
       raise ValueError("qei_scorer must be 'torch' or 'hip', got "
                        f'{self._config.qei_scorer!r}')
+    if self._config.linear_scorer not in ('torch', 'hip'):
+      raise ValueError("linear_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.linear_scorer!r}')
     self._seed = seed
     self._trials: List[vz.Trial] = []
     self._converter = TrialToArrayConverter(problem)
@@ -290,7 +303,8 @@ class VizierGPBandit(Designer, Predictor):
         from vizier_amd._src.gp import linear_matern
         post = linear_matern.train_linear_matern_gp(
             x, y, linear_coef=cfg.linear_coef, num_restarts=restarts,
-            max_iters=iters, seed=self._seed, warm_start_raw=warm)
+            max_iters=iters, seed=self._seed, warm_start_raw=warm,
+            with_k_inv=cfg.linear_scorer == 'hip')
       else:
         post = gp_model.train_gp(
             x, y, num_restarts=restarts, max_iters=iters,
@@ -496,6 +510,20 @@ class VizierGPBandit(Designer, Predictor):
       else:
         acquisition = acq_lib.UCB(coefficient=cfg.ucb_coefficient)
       composed = posterior
+      if getattr(posterior, 'K_inv_lin', None) is not None:
+        # linear_scorer='hip': ScoringFunction takes the fused Matern +
+        # linear scorer where it applies (no host sync: capture-eligible)
+        # and predict() elsewhere. Deliberately NOT exposed as
+        # score_fn.scoring: the megakernels are pure-Matern.
+        scoring = acq_lib.ScoringFunction(
+            posterior, acquisition, trust_region,
+            gram_dtype=cfg.scorer_gram_dtype)
+
+        def score_fn(batch: CandidateBatch) -> torch.Tensor:
+          dense = self._codec.decode(batch)[:, 0, :]
+          return scoring(dense)
+        score_fn.graph_safe = scoring.linear_hip_applies(self._x)
+        return score_fn, 1
 
       def score_fn(batch: CandidateBatch) -> torch.Tensor:
         dense = self._codec.decode(batch)[:, 0, :]

@@ -603,6 +603,37 @@ class ScoringFunction:
     else:
       self._tr_radius = 0.0
       self._tr_anchored = True
+    # Matern + linear kernel posterior fitted with its combined-kernel
+    # inverse (linear_matern.train_linear_matern_gp(with_k_inv=True)): the
+    # fused posterior_score_linear.hip scorer. slope and shift are hoisted
+    # here, already multiplied by linear_coef.
+    self._lin_kinv = getattr(posterior, 'K_inv_lin', None)
+    if self._lin_kinv is not None:
+      lc = float(posterior.linear_coef)
+      self._lin_slope = lc * float(posterior.params.slope)
+      self._lin_shift = lc * float(posterior.params.shift)
+
+  def linear_hip_applies(self, xs: torch.Tensor) -> bool:
+    """The fused Matern + linear HIP scorer serves `xs`; otherwise a
+    linear-kernel posterior scores through predict()."""
+    return (self._lin_kinv is not None and xs.is_cuda and
+            xs.dtype == torch.float32 and self._acq_name is not None and
+            self._tr_anchored and self.gram_dtype == 'fp32')
+
+  def _call_linear_hip(self, xs: torch.Tensor) -> torch.Tensor:
+    post = self.posterior
+    from vizier_amd._src.ops import dispatch as ops
+    onehot = self._onehot_u8
+    if onehot is None:
+      onehot = torch.zeros(xs.shape[-1], dtype=torch.uint8,
+                           device=xs.device)
+      self._onehot_u8 = onehot
+    ext = ops.require_ext()
+    return ext.posterior_scores_linear(
+        xs, post.x, post.params.lengthscales, self._amp, self._mean_c,
+        self._lin_slope, self._lin_shift, post.alpha, self._lin_kinv,
+        onehot, ops.ACQ_CODES[self._acq_name], self._coef, self._best,
+        self._tr_radius if self.trust_region is not None else 0.0)
 
   def _can_fuse(self, xs: torch.Tensor) -> bool:
     """True when the GPU K^-1 quadform path applies (any acquisition).
@@ -713,6 +744,8 @@ class ScoringFunction:
       if self.trust_region is not None:
         scores = self.trust_region.apply(xs, scores)
       return scores
+    if self.linear_hip_applies(xs):
+      return self._call_linear_hip(xs)
     mean, stddev = self.posterior.predict(xs)
     scores = self.acquisition(mean, stddev)
     if self.trust_region is not None:

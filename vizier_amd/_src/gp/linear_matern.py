@@ -13,8 +13,12 @@ term captures global trends that a stationary kernel models poorly
 (high-D or drifting objectives).
 
 MI355X note: posteriors from this model deliberately publish
-K_inv=None so ScoringFunction routes through predict() (the combined
-kernel) instead of the fused pure-Matérn HIP scorers.
+K_inv=None, so nothing mistakes them for a pure-Matérn posterior and
+hands them to the pure-Matérn HIP scorers. By default ScoringFunction
+routes them through predict() (the combined kernel, eager torch). With
+`with_k_inv=True` the fit also caches `K_inv_lin`, the inverse of the
+COMBINED kernel's Gram, and ScoringFunction scores through the fused
+Matérn + linear HIP scorer (ops/csrc/posterior_score_linear.hip).
 """
 
 from __future__ import annotations
@@ -105,7 +109,8 @@ class LinearMaternPosterior:
   """Cached posterior for the combined kernel.
 
   Duck-type compatible with gp_model.GPPosterior where the designers
-  need it; K_inv is always None (see module pydoc)."""
+  need it; K_inv is always None (see module pydoc). K_inv_lin, when the
+  fit was asked for it, is (K_combined + noise_eff I)^-1 in x's dtype."""
 
   x: torch.Tensor
   params: LinearMaternParams
@@ -116,6 +121,7 @@ class LinearMaternPosterior:
   raw: Optional[torch.Tensor] = None
   aux: Optional[torch.Tensor] = None  # [slope, shift] for broadcasts
   noise_eff: float = 0.0     # cache noise floor actually used
+  K_inv_lin: Optional[torch.Tensor] = None  # (N, N), combined kernel
 
   @property
   def K_inv(self):
@@ -141,9 +147,11 @@ class LinearMaternPosterior:
 def train_linear_matern_gp(
     x: torch.Tensor, y: torch.Tensor, *, linear_coef: float,
     num_restarts: int = 4, max_iters: int = 50, seed: int = 0,
-    warm_start_raw: Optional[torch.Tensor] = None
-    ) -> LinearMaternPosterior:
-  """Fits the combined-kernel GP (restarted batched L-BFGS)."""
+    warm_start_raw: Optional[torch.Tensor] = None,
+    with_k_inv: bool = False) -> LinearMaternPosterior:
+  """Fits the combined-kernel GP (restarted batched L-BFGS).
+
+  with_k_inv: also cache K_inv_lin for the fused HIP scorer."""
   x = x.detach()
   y = y.detach().reshape(-1)
   n, d = x.shape
@@ -181,6 +189,13 @@ def train_linear_matern_gp(
   resid = (y.double() - p64.mean).unsqueeze(-1)
   z = torch.linalg.solve_triangular(L64, resid, upper=False)
   alpha = torch.linalg.solve_triangular(L64.mT, z, upper=True).squeeze(-1)
+  k_inv = None
+  if with_k_inv:
+    # Formed in fp64 from the fp64 factor, rounded once (as
+    # gp_model._build_posterior_cache does).
+    eye = torch.eye(n, dtype=x64.dtype, device=x.device)
+    zi = torch.linalg.solve_triangular(L64, eye, upper=False)
+    k_inv = (zi.mT @ zi).to(x.dtype)
   params = LinearMaternParams.from_raw(raw)
   return LinearMaternPosterior(
       x=x, params=params, linear_coef=linear_coef, L=L64.to(x.dtype),
@@ -188,4 +203,4 @@ def train_linear_matern_gp(
       raw=raw.detach(),
       aux=torch.stack([params.slope.reshape(()),
                        params.shift.reshape(())]),
-      noise_eff=float(noise_eff))
+      noise_eff=float(noise_eff), K_inv_lin=k_inv)

@@ -116,6 +116,24 @@ extern "C" void launch_ps_quadform_finalize(
     float amp2, float mean_c, int acq, float coef, float best_value,
     float tr_radius, hipStream_t stream);
 
+// Matern + linear kernel scorer (posterior_score_linear.hip).
+extern "C" int psl_num_tiles(int n);
+extern "C" void launch_psl_kvec(
+    const float* xq, const float* x, const float* inv_ls,
+    const float* alpha, const unsigned char* onehot, float* k_ws,
+    float* mu_part, float* dist_part, float* zq2, int b, int n, int d,
+    float amp2, float s2, float cshift, hipStream_t stream);
+extern "C" void launch_psl_finalize_score(
+    const float* mu_part, const float* dist_part, const float* zq2,
+    const float* quad, float* out, int b, int tiles, float amp2, float s2,
+    float mean_c, int acq, float coef, float best_value, float tr_radius,
+    hipStream_t stream);
+extern "C" void launch_psl_finalize_meanstd(
+    const float* mu_part, const float* dist_part, const float* zq2,
+    const float* quad, float* mean_out, float* sd_out, float* dist_out,
+    int b, int tiles, float amp2, float s2, float mean_c,
+    hipStream_t stream);
+
 extern "C" void launch_qei_cov(
     const float* t_ws, const float* k_ws, const float* mu_ws,
     const float* xs, const float* inv_ls, float* mean_out, float* cov_out,
@@ -1012,6 +1030,103 @@ std::vector<torch::Tensor> posterior_mean_std_fp8(
                           (float)mean_c);
 }
 
+// -- Matern + linear kernel scorer (posterior_score_linear.hip) -----------
+
+namespace {
+
+// Everything the two linear bindings share up to the finalize: checks, the
+// tile-owner k-vector kernel, the shared quadform. No host sync anywhere,
+// so the chain is stream-capturable.
+struct LinearScorerRun {
+  ScorerWs ws;
+  torch::Tensor part;  // (2, b, tiles): mu partial sums, dist partial mins
+  torch::Tensor zq2;   // (b,) |zq|^2 of the per-candidate prior
+  torch::Tensor quad;  // (b,) k^T kinv k
+  int b, tiles;
+  float amp2, s2;
+  const float* mu_part() const { return part.data_ptr<float>(); }
+  const float* dist_part() const {
+    return part.data_ptr<float>() + (int64_t)b * tiles;
+  }
+};
+
+LinearScorerRun linear_scorer_run(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double slope, double shift, torch::Tensor alpha,
+    torch::Tensor kinv, torch::Tensor onehot) {
+  xq = check_f32(xq, "xq");
+  x = check_f32(x, "x");
+  lengthscales = check_f32(lengthscales, "lengthscales");
+  alpha = check_f32(alpha, "alpha");
+  kinv = check_f32(kinv, "kinv");
+  check_scorer_args(xq, x, lengthscales, alpha, kinv, onehot);
+  onehot = onehot.contiguous();
+  const int64_t b = xq.size(0), d = xq.size(1), n = x.size(0);
+  TORCH_CHECK(d <= 512, "the linear scorer supports D <= 512, got ", d);
+  TORCH_CHECK(b >= 1 && n >= 1, "the linear scorer needs at least one "
+              "candidate and one training row, got ", b, " and ", n);
+  TORCH_CHECK(b * n < (int64_t{1} << 31) && n * d < (int64_t{1} << 31),
+              "the linear scorer's workspace is too large");
+  auto inv_ls = 1.0f / lengthscales;
+  const int tiles = psl_num_tiles((int)n);
+  LinearScorerRun run{ScorerWs(xq, (int)n),
+                      torch::empty({2, b, tiles}, xq.options()),
+                      torch::empty({b}, xq.options()),
+                      torch::Tensor(),
+                      (int)b,
+                      tiles,
+                      (float)(amplitude * amplitude),
+                      (float)(slope * slope)};
+  launch_psl_kvec(
+      xq.data_ptr<float>(), x.data_ptr<float>(), inv_ls.data_ptr<float>(),
+      alpha.data_ptr<float>(), onehot.data_ptr<unsigned char>(),
+      run.ws.k.data_ptr<float>(), run.part.data_ptr<float>(),
+      run.part.data_ptr<float>() + b * tiles, run.zq2.data_ptr<float>(),
+      (int)b, (int)n, (int)d, run.amp2, run.s2, (float)shift,
+      current_stream());
+  // The tile quadform holds 32 candidates; everything else, b > 32 below
+  // the threshold included, takes the GEMM. The legacy NCHUNK route is not
+  // offered here.
+  const QuadRoute route = quad_route((int)n, (int)b) == QuadRoute::kTile
+      ? QuadRoute::kTile : QuadRoute::kGemm;
+  run.quad = quadform(route, run.ws, kinv).contiguous();
+  return run;
+}
+
+}  // namespace
+
+// slope and shift arrive already multiplied by linear_coef.
+torch::Tensor posterior_scores_linear(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, double slope, double shift,
+    torch::Tensor alpha, torch::Tensor kinv, torch::Tensor onehot,
+    int64_t acq, double coef, double best_value, double tr_radius) {
+  auto run = linear_scorer_run(xq, x, lengthscales, amplitude, slope, shift,
+                               alpha, kinv, onehot);
+  auto out = torch::empty({run.b}, run.zq2.options());
+  launch_psl_finalize_score(
+      run.mu_part(), run.dist_part(), run.zq2.data_ptr<float>(),
+      run.quad.data_ptr<float>(), out.data_ptr<float>(), run.b, run.tiles,
+      run.amp2, run.s2, (float)mean_c, (int)acq, (float)coef,
+      (float)best_value, (float)tr_radius, current_stream());
+  return out;
+}
+
+std::vector<torch::Tensor> posterior_mean_std_linear(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    double amplitude, double mean_c, double slope, double shift,
+    torch::Tensor alpha, torch::Tensor kinv, torch::Tensor onehot) {
+  auto run = linear_scorer_run(xq, x, lengthscales, amplitude, slope, shift,
+                               alpha, kinv, onehot);
+  auto sd = torch::empty({run.b}, run.zq2.options());
+  launch_psl_finalize_meanstd(
+      run.mu_part(), run.dist_part(), run.zq2.data_ptr<float>(),
+      run.quad.data_ptr<float>(), run.ws.mu.data_ptr<float>(),
+      sd.data_ptr<float>(), run.ws.dist.data_ptr<float>(), run.b, run.tiles,
+      run.amp2, run.s2, (float)mean_c, current_stream());
+  return {run.ws.mu, sd, run.ws.dist};
+}
+
 // -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
 
 namespace {
@@ -1895,6 +2010,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Hypervolume scalarization + trust region in one launch");
   m.def("posterior_scores_bf16", &posterior_scores_bf16,
         "Chunked scorer with cached-bf16 candidate grams (gfx950)");
+  m.def("posterior_scores_linear", &posterior_scores_linear,
+        "Matern + linear kernel posterior + acquisition (gfx950)");
+  m.def("posterior_mean_std_linear", &posterior_mean_std_linear,
+        "Matern + linear kernel (mean, sd, min-Linf dist) (gfx950)");
   m.def("posterior_scores_chunked", &posterior_scores_chunked,
         "3-kernel chunked GP posterior scorer (chip-filling, gfx950)");
   m.def("qei_joint_mean_cov", &qei_joint_mean_cov,

@@ -106,6 +106,16 @@ class GPBanditConfig:
   # or 'separable'/'separable_diag' joint task kernels
   # (gp_bandit.py:157 _multitask_type; multitask_tuned_gp_models.py:41).
   multitask_type: str = 'independent'
+  # Scorer of a 'separable' / 'separable_diag' surrogate: 'torch' (default:
+  # MultitaskPosterior.predict, eager sweep) or 'hip' (opt-in, GPU +
+  # float32 only: the fit also builds MultitaskFusedCache and the sweep
+  # scores through the fused posterior_score_multitask.hip scorer, captured
+  # in a hipGraph). M > 8, N >= 4096, D > 512 or a trust region that is not
+  # anchored at the training points keep the torch path. The variance then
+  # comes from fp32 quadforms instead of a triangular solve, the cache uses
+  # no fit-time jitter and the captured sweep selects from the final pool,
+  # so suggestions can differ from 'torch'.
+  multitask_scorer: str = 'torch'
   # Custom acquisition hook (gp_bandit.py:132 _scoring_function_factory):
   # called as factory(posterior, best_value, trust_region) -> callable
   # mapping xs (B, D) -> scores (B,). Overrides `acquisition`; runs on
@@ -133,6 +143,9 @@ class VizierGPBandit(Designer, Predictor):
     if self._config.linear_scorer not in ('torch', 'hip'):
       raise ValueError("linear_scorer must be 'torch' or 'hip', got "
                        f'{self._config.linear_scorer!r}')
+    if self._config.multitask_scorer not in ('torch', 'hip'):
+      raise ValueError("multitask_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.multitask_scorer!r}')
     self._seed = seed
     self._trials: List[vz.Trial] = []
     self._converter = TrialToArrayConverter(problem)
@@ -265,6 +278,8 @@ class VizierGPBandit(Designer, Predictor):
               if cfg.multitask_type == 'separable_diag'
               else multitask.MultiTaskType.SEPARABLE)
       y_all = torch.as_tensor(y_np, dtype=cfg.dtype, device=self._device)
+      if cfg.multitask_scorer == 'hip':
+        check_multitask_hip(x)
       warm = self._mt_posterior.raw if (cfg.warm_refit and
                                         self._mt_posterior is not None) \
           else None
@@ -274,7 +289,8 @@ class VizierGPBandit(Designer, Predictor):
           else cfg.ard_restarts,
           max_iters=cfg.ard_warm_iters if warm is not None
           else cfg.ard_max_iters,
-          seed=self._seed, warm_start_raw=warm)
+          seed=self._seed, warm_start_raw=warm,
+          with_fused_cache=cfg.multitask_scorer == 'hip')
       self._posteriors = [
           _MultitaskTaskView(self._mt_posterior, t)
           for t in range(y_np.shape[1])]
@@ -438,6 +454,11 @@ class VizierGPBandit(Designer, Predictor):
         return mean, var.sqrt()
 
       mt = self._mt_posterior
+      if mt is not None and mt.fused is not None:
+        hip_score_fn = multitask_hip_score_fn(
+            mt, self._codec, scalarizer, trust_region, cfg.ucb_coefficient)
+        if hip_score_fn is not None:
+          return hip_score_fn, 1
 
       def score_fn(batch: CandidateBatch) -> torch.Tensor:
         dense = self._codec.decode(batch)
@@ -764,6 +785,53 @@ class _MultitaskTaskView:
   def predict(self, xq: torch.Tensor):
     mean, stddev = self._mt.predict(xq)
     return mean[:, self.task], stddev[:, self.task]
+
+
+def check_multitask_hip(x: torch.Tensor) -> None:
+  if not x.is_cuda or x.dtype != torch.float32:
+    raise ValueError(
+        "multitask_scorer='hip' needs a GPU device and dtype float32, got "
+        f'device {x.device} and {x.dtype}')
+
+
+def multitask_hip_score_fn(mt, codec, scalarizer, trust_region,
+                           ucb_coefficient: float):
+  """Scalarized UCB of a joint multitask posterior on the fused scorer
+  (multitask_scorer='hip'): decode -> multitask_mean_std -> hv_scalarize_tr,
+  no host sync. None where the kernels do not apply (their shape limits; a
+  trust region not anchored at the posterior's own x, whose distance the
+  kernel could not give): the caller keeps its torch closure."""
+  f = mt.fused
+  n, d = mt.x.shape
+  if f.w.shape[0] > 8 or n >= 4096 or d > 512:
+    return None
+  if trust_region is not None and not (
+      trust_region._trusted.shape == mt.x.shape and
+      trust_region._trusted.data_ptr() == mt.x.data_ptr()):
+    return None
+  from vizier_amd._src.ops import dispatch as ops
+  ext = ops.require_ext()
+  weights = scalarizer.weights.to(mt.x.device, torch.float32).contiguous()
+  ref = scalarizer.reference_point
+  ref = (ref.to(mt.x.device, torch.float32).contiguous()
+         if ref is not None else None)
+  onehot = (trust_region._onehot.to(torch.uint8).contiguous()
+            if trust_region is not None else
+            torch.zeros(d, dtype=torch.uint8, device=mt.x.device))
+  tr_radius = (float(trust_region.trust_radius)
+               if trust_region is not None else 0.0)
+  x = mt.x.contiguous()
+
+  def score_fn(batch: CandidateBatch) -> torch.Tensor:
+    xs = codec.decode(batch)[:, 0, :].contiguous()
+    means, sds, dist = ext.multitask_mean_std(
+        xs, x, f.lengthscales, f.means, f.a_mat, f.w, f.c, f.bdiag, onehot)
+    return ext.hv_scalarize_tr(
+        means, sds, weights, ref,
+        dist if trust_region is not None else None,
+        ucb_coefficient, tr_radius)
+  score_fn.graph_safe = True
+  return score_fn
 
 
 def posterior_batched_cov(posterior: gp_model.GPPosterior,

@@ -61,6 +61,13 @@ class UCBPEConfig:
   # Multimetric surrogate (gp_ucb_pe.py:129 multitask_type):
   # 'independent' per-metric GPs or 'separable'/'separable_diag' joint.
   multitask_type: str = 'independent'
+  # Scorer of a 'separable' / 'separable_diag' surrogate in the UCB phase:
+  # 'torch' (default: one joint predict per metric view, eager sweep) or
+  # 'hip' (opt-in, GPU + float32 only: the fused
+  # posterior_score_multitask.hip scorer, captured in a hipGraph; see
+  # GPBanditConfig.multitask_scorer). Pending trials, the PE phase, the set
+  # phase and shapes beyond the kernels' limits keep the torch path.
+  multitask_scorer: str = 'torch'
   signal_to_noise_threshold: float = 0.7
   # Batch PE via the SET acquisition (gp_ucb_pe.py:118,510): the
   # exploration members of a batch are optimized JOINTLY, scored by the
@@ -101,6 +108,9 @@ class VizierGPUCBPEBandit(Designer):
     if self._config.set_pe_scorer not in ('torch', 'hip'):
       raise ValueError("set_pe_scorer must be 'torch' or 'hip', got "
                        f'{self._config.set_pe_scorer!r}')
+    if self._config.multitask_scorer not in ('torch', 'hip'):
+      raise ValueError("multitask_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.multitask_scorer!r}')
     self._seed = seed
     self._rng = np.random.default_rng(seed)
     self._completed: List[vz.Trial] = []
@@ -241,13 +251,16 @@ class VizierGPUCBPEBandit(Designer):
         y_all = torch.as_tensor(warped, dtype=cfg.dtype,
                                 device=self._device)
         warm = self._mt_raw
+        if cfg.multitask_scorer == 'hip':
+          gp_bandit.check_multitask_hip(x)
         mt = multitask.train_multitask_gp(
             x, y_all, multitask_type=kind,
             num_restarts=cfg.ard_warm_restarts if warm is not None
             else cfg.ard_restarts,
             max_iters=cfg.ard_warm_iters if warm is not None
             else cfg.ard_max_iters,
-            seed=self._seed, warm_start_raw=warm)
+            seed=self._seed, warm_start_raw=warm,
+            with_fused_cache=cfg.multitask_scorer == 'hip')
         self._mt_raw = mt.raw
         posts = [_MultitaskTaskView(mt, t)
                  for t in range(y_np.shape[1])]
@@ -566,7 +579,16 @@ class VizierGPUCBPEBandit(Designer):
             dist = dist_src
           return means, sds, dist
 
-      if use_ucb:
+      mt = getattr(posts[0], '_mt', None)
+      hip_score_fn = None
+      if (use_ucb and mt is not None and mt.fused is not None and
+          mt.x.shape == x_all.shape and
+          mt.x.data_ptr() == x_all.data_ptr()):
+        hip_score_fn = gp_bandit.multitask_hip_score_fn(
+            mt, self._codec, scalarizer, trust_region, cfg.ucb_coefficient)
+      if hip_score_fn is not None:
+        score_fn = hip_score_fn
+      elif use_ucb:
         if fused_mo and self._fusable(posts[0], x_all):
           # Fused MO UCB (same shape as GP-Bandit's config-5 path):
           # per-metric (mean, sd, dist) kernels + ONE scalarize+TR

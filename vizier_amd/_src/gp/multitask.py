@@ -125,6 +125,54 @@ def negative_log_marginal_likelihood(raw: torch.Tensor, x: torch.Tensor,
 
 
 @dataclasses.dataclass
+class MultitaskFusedCache:
+  """Operands of the fused HIP scorer (posterior_score_multitask.hip).
+
+  With B = U diag(lam) U^T the joint K = Kx (x) B + tau I splits into M
+  systems W_s = (lam_s Kx + tau I)^-1 of size N (Kx: unit-amplitude Gram):
+    var_t  = B_tt - sum_s c[t, s] kx^T W_s kx,  c[t, s] = lam_s^2 U[t, s]^2
+    mean_t = means_t + kx . a_mat[:, t],        a_mat = alpha_mat B
+  Each W_s is conditioned like a single-task GP with the 1e-3 floor, unlike
+  the (NM)^2 inverse. Built in float64, stored in the working dtype.
+  """
+
+  w: torch.Tensor              # (M, N, N), each exactly symmetric
+  c: torch.Tensor              # (M, M)
+  bdiag: torch.Tensor          # (M,)
+  a_mat: torch.Tensor          # (N, M)
+  means: torch.Tensor          # (M,)
+  lengthscales: torch.Tensor   # (D,)
+  noise_eff: float             # tau: fitted noise + conditioning floor
+
+
+def _build_fused_cache(x: torch.Tensor, params: 'MultitaskParams',
+                       alpha_mat: torch.Tensor,
+                       noise_eff: torch.Tensor) -> MultitaskFusedCache:
+  x64 = x.double()
+  ls64 = params.lengthscales.double()
+  b64 = params.task_cov.double()
+  kx = gram_matern52(x64, None, ls64,
+                     torch.ones((), dtype=torch.float64, device=x.device))
+  # A rank-deficient B gives eigenvalues like -4e-16.
+  lam, u = torch.linalg.eigh(b64)
+  lam = lam.clamp_min(0.0)
+  eye = torch.eye(x.shape[0], dtype=torch.float64, device=x.device)
+  tau = noise_eff.double()
+  w = []
+  for s in range(lam.numel()):
+    inv = torch.cholesky_inverse(torch.linalg.cholesky(lam[s] * kx +
+                                                       tau * eye))
+    w.append(0.5 * (inv + inv.T))   # exactly symmetric: the kernel reads
+                                    # only the upper-triangular tiles
+  to = lambda t: t.to(x.dtype).contiguous()
+  return MultitaskFusedCache(
+      w=to(torch.stack(w)), c=to((lam * lam) * (u * u)),
+      bdiag=to(b64.diagonal()), a_mat=to(alpha_mat.double() @ b64),
+      means=to(params.means.double()), lengthscales=to(ls64),
+      noise_eff=float(tau))
+
+
+@dataclasses.dataclass
 class MultitaskPosterior:
   """Cached joint posterior; predict() returns per-task marginals."""
 
@@ -140,6 +188,8 @@ class MultitaskPosterior:
   K_inv: Optional[torch.Tensor]
   nll: float
   raw: Optional[torch.Tensor] = None
+  # multitask_scorer='hip': operands of the fused HIP scorer.
+  fused: Optional[MultitaskFusedCache] = None
 
   def predict(self, xq: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(Q, D) -> mean (Q, M), stddev (Q, M)."""
@@ -166,7 +216,8 @@ def train_multitask_gp(x: torch.Tensor, y: torch.Tensor, *,
                        MultiTaskType.SEPARABLE,
                        num_restarts: int = 4, max_iters: int = 50,
                        seed: int = 0, precompute_inverse: bool = False,
-                       warm_start_raw: Optional[torch.Tensor] = None
+                       warm_start_raw: Optional[torch.Tensor] = None,
+                       with_fused_cache: bool = False
                        ) -> MultitaskPosterior:
   """Fits the separable multitask GP by batched restarted L-BFGS."""
   if multitask_type == MultiTaskType.INDEPENDENT:
@@ -202,8 +253,27 @@ def train_multitask_gp(x: torch.Tensor, y: torch.Tensor, *,
   raw = best_raw[idx]
   params = MultitaskParams.from_raw(raw, d, m, multitask_type)
 
+  post = posterior_from_params(x, y, params,
+                               precompute_inverse=precompute_inverse,
+                               with_fused_cache=with_fused_cache)
+  post.nll = float(best_f[idx])
+  post.raw = raw.detach()
+  return post
+
+
+def posterior_from_params(x: torch.Tensor, y: torch.Tensor,
+                          params: MultitaskParams, *,
+                          precompute_inverse: bool = False,
+                          with_fused_cache: bool = False
+                          ) -> MultitaskPosterior:
+  """The posterior at given (unbatched) hyperparameters: floor, joint
+  factor, alpha and, on request, the fused scorer's cache."""
+  n, m = y.shape
+  pb = MultitaskParams(noise=params.noise.reshape(1),
+                       means=params.means.unsqueeze(0),
+                       lengthscales=params.lengthscales.unsqueeze(0),
+                       task_chol=params.task_chol.unsqueeze(0))
   # Same fp32 conditioning floor as gp_model.train_gp's cache build.
-  pb = MultitaskParams.from_raw(raw.unsqueeze(0), d, m, multitask_type)
   k = _joint_cov(pb, x)[0]
   floor = (1e-3 * params.task_cov.diagonal().max() - params.noise
            ).clamp_min(0.0)
@@ -217,9 +287,10 @@ def train_multitask_gp(x: torch.Tensor, y: torch.Tensor, *,
     eye = torch.eye(n * m, dtype=x.dtype, device=x.device)
     z = torch.linalg.solve_triangular(L, eye, upper=False)
     k_inv = z.T @ z
+  fused = _build_fused_cache(x, params, alpha, params.noise + floor) \
+      if with_fused_cache else None
   return MultitaskPosterior(x=x, params=params, L=L, alpha_mat=alpha,
-                            K_inv=k_inv, nll=float(best_f[idx]),
-                            raw=raw.detach())
+                            K_inv=k_inv, nll=float('nan'), fused=fused)
 
 
 def train_independent_gps(x: torch.Tensor, y: torch.Tensor, *,

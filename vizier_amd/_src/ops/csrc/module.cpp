@@ -134,6 +134,16 @@ extern "C" void launch_psl_finalize_meanstd(
     int b, int tiles, float amp2, float s2, float mean_c,
     hipStream_t stream);
 
+// Separable multitask GP scorer (posterior_score_multitask.hip).
+extern "C" int mt_num_tiles(int n);
+extern "C" int mt_num_items(int n);
+extern "C" void launch_mt_mean_std(
+    const float* xq, const float* x, const float* inv_ls, const float* a_mat,
+    const float* w, const float* c, const float* bdiag, const float* means,
+    const unsigned char* onehot, float* k_ws, float* part, float* mu_part,
+    float* dist_part, float* mean_out, float* sd_out, float* dist_out, int b,
+    int n, int d, int m, hipStream_t stream);
+
 extern "C" void launch_qei_cov(
     const float* t_ws, const float* k_ws, const float* mu_ws,
     const float* xs, const float* inv_ls, float* mean_out, float* cov_out,
@@ -1127,6 +1137,70 @@ std::vector<torch::Tensor> posterior_mean_std_linear(
   return {run.ws.mu, sd, run.ws.dist};
 }
 
+// -- Separable multitask GP scorer (posterior_score_multitask.hip) ---------
+
+// Operands of multitask.MultitaskFusedCache. Returns means (M, b), sds
+// (M, b), dist (b): hv_scalarize_tr's layout. Every check precedes the one
+// launch sequence; no host sync, so the chain is stream-capturable.
+std::vector<torch::Tensor> multitask_mean_std(
+    torch::Tensor xq, torch::Tensor x, torch::Tensor lengthscales,
+    torch::Tensor means, torch::Tensor a_mat, torch::Tensor w,
+    torch::Tensor c, torch::Tensor bdiag, torch::Tensor onehot) {
+  for (const auto* t : {&xq, &x, &lengthscales, &means, &a_mat, &w, &c,
+                        &bdiag}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                t->is_contiguous(),
+                "multitask_mean_std takes contiguous fp32 GPU tensors");
+  }
+  TORCH_CHECK(onehot.scalar_type() == torch::kUInt8 && onehot.is_cuda() &&
+              onehot.is_contiguous(),
+              "onehot must be a contiguous uint8 GPU tensor");
+  TORCH_CHECK(xq.dim() == 2 && x.dim() == 2, "xq and x must be 2-D");
+  const int64_t b = xq.size(0), d = xq.size(1), n = x.size(0);
+  TORCH_CHECK(x.size(1) == d, "x must have xq's ", d, " columns, got ",
+              x.size(1));
+  TORCH_CHECK(b >= 1 && n >= 1 && d >= 1, "the multitask scorer needs at "
+              "least one candidate, training row and column");
+  TORCH_CHECK(d <= 512, "the multitask scorer supports D <= 512, got ", d);
+  TORCH_CHECK(n < 4096, "the multitask scorer supports N < 4096, got ", n);
+  TORCH_CHECK(w.dim() == 3, "w must be (M, N, N)");
+  const int64_t m = w.size(0);
+  TORCH_CHECK(m >= 1 && m <= 8, "the multitask scorer supports 1 <= M <= 8, "
+              "got ", m);
+  TORCH_CHECK(w.size(1) == n && w.size(2) == n, "w must be (", m, ", ", n,
+              ", ", n, ")");
+  TORCH_CHECK(a_mat.dim() == 2 && a_mat.size(0) == n && a_mat.size(1) == m,
+              "a_mat must be (", n, ", ", m, ")");
+  TORCH_CHECK(c.dim() == 2 && c.size(0) == m && c.size(1) == m,
+              "c must be (", m, ", ", m, ")");
+  TORCH_CHECK(bdiag.numel() == m && means.numel() == m,
+              "bdiag and means must have ", m, " elements");
+  TORCH_CHECK(lengthscales.numel() == d && onehot.numel() == d,
+              "lengthscales and onehot must have ", d, " elements");
+  TORCH_CHECK(b * n < (int64_t{1} << 31) &&
+              b * m * mt_num_items((int)n) < (int64_t{1} << 31),
+              "the multitask scorer's workspace is too large");
+  auto inv_ls = 1.0f / lengthscales;
+  const int64_t tiles = mt_num_tiles((int)n), items = mt_num_items((int)n);
+  auto k_ws = torch::empty({b, n}, xq.options());
+  auto part = torch::empty({b, m, items}, xq.options());
+  auto mu_part = torch::empty({b, m, tiles}, xq.options());
+  auto dist_part = torch::empty({b, tiles}, xq.options());
+  auto mean_out = torch::empty({m, b}, xq.options());
+  auto sd_out = torch::empty({m, b}, xq.options());
+  auto dist_out = torch::empty({b}, xq.options());
+  launch_mt_mean_std(
+      xq.data_ptr<float>(), x.data_ptr<float>(), inv_ls.data_ptr<float>(),
+      a_mat.data_ptr<float>(), w.data_ptr<float>(), c.data_ptr<float>(),
+      bdiag.data_ptr<float>(), means.data_ptr<float>(),
+      onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
+      part.data_ptr<float>(), mu_part.data_ptr<float>(),
+      dist_part.data_ptr<float>(), mean_out.data_ptr<float>(),
+      sd_out.data_ptr<float>(), dist_out.data_ptr<float>(), (int)b, (int)n,
+      (int)d, (int)m, current_stream());
+  return {mean_out, sd_out, dist_out};
+}
+
 // -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
 
 namespace {
@@ -2014,6 +2088,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Matern + linear kernel posterior + acquisition (gfx950)");
   m.def("posterior_mean_std_linear", &posterior_mean_std_linear,
         "Matern + linear kernel (mean, sd, min-Linf dist) (gfx950)");
+  m.def("multitask_mean_std", &multitask_mean_std,
+        "Separable multitask GP (means, sds, min-Linf dist) (gfx950)");
   m.def("posterior_scores_chunked", &posterior_scores_chunked,
         "3-kernel chunked GP posterior scorer (chip-filling, gfx950)");
   m.def("qei_joint_mean_cov", &qei_joint_mean_cov,

@@ -116,6 +116,17 @@ class GPBanditConfig:
   # no fit-time jitter and the captured sweep selects from the final pool,
   # so suggestions can differ from 'torch'.
   multitask_scorer: str = 'torch'
+  # Scorer of the surrogates that combine several Matern GPs, the
+  # ensemble_size > 1 mixture and the set_priors() transfer stack: 'torch'
+  # (default: member by member through predict(), eager sweep) or 'hip'
+  # (opt-in, GPU + float32 only: one acq_lib.GroupScoringFunction call on the
+  # posterior_score_group.hip kernels, captured in a hipGraph). 'hip' serves
+  # UCB / EI / PI over at most 8 plain GPPosteriors with K_inv, D <= 512,
+  # every N < 4096 and a trust region anchored at the training points;
+  # anything else (Thompson, an ensemble on top of priors, ...) keeps the
+  # torch closure. The captured sweep selects from the final pool and sums
+  # in another order, so suggestions can differ from 'torch'.
+  group_scorer: str = 'torch'
   # Custom acquisition hook (gp_bandit.py:132 _scoring_function_factory):
   # called as factory(posterior, best_value, trust_region) -> callable
   # mapping xs (B, D) -> scores (B,). Overrides `acquisition`; runs on
@@ -146,6 +157,9 @@ class VizierGPBandit(Designer, Predictor):
     if self._config.multitask_scorer not in ('torch', 'hip'):
       raise ValueError("multitask_scorer must be 'torch' or 'hip', got "
                        f'{self._config.multitask_scorer!r}')
+    if self._config.group_scorer not in ('torch', 'hip'):
+      raise ValueError("group_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.group_scorer!r}')
     self._seed = seed
     self._trials: List[vz.Trial] = []
     self._converter = TrialToArrayConverter(problem)
@@ -509,6 +523,13 @@ class VizierGPBandit(Designer, Predictor):
       else:
         acquisition = acq_lib.UCB(coefficient=cfg.ucb_coefficient)
       stacked = self._stacked
+      if cfg.group_scorer == 'hip':
+        levels = stacked.levels()
+        hip_score_fn = self._group_hip_score_fn(
+            [p for p, _ in levels], [1.0] * len(levels),
+            [w for _, w in levels], 0.0, acquisition, trust_region)
+        if hip_score_fn is not None:
+          return hip_score_fn, 1
 
       def score_fn(batch: CandidateBatch) -> torch.Tensor:
         dense = self._codec.decode(batch)[:, 0, :]
@@ -545,6 +566,14 @@ class VizierGPBandit(Designer, Predictor):
           return scoring(dense)
         score_fn.graph_safe = scoring.linear_hip_applies(self._x)
         return score_fn, 1
+      if cfg.group_scorer == 'hip' and isinstance(
+          posterior, gp_model.EnsembleGPPosterior):
+        share = 1.0 / len(posterior.members)
+        hip_score_fn = self._group_hip_score_fn(
+            posterior.members, [share] * len(posterior.members),
+            [share] * len(posterior.members), 1.0, acquisition, trust_region)
+        if hip_score_fn is not None:
+          return hip_score_fn, 1
 
       def score_fn(batch: CandidateBatch) -> torch.Tensor:
         dense = self._codec.decode(batch)[:, 0, :]
@@ -632,6 +661,25 @@ class VizierGPBandit(Designer, Predictor):
     # the codec's column maps.
     score_fn.codec = self._codec
     return score_fn, 1
+
+  def _group_hip_score_fn(self, members, a, w, c, acquisition, trust_region):
+    """Ensemble mixture / transfer stack on the posterior_score_group.hip
+    kernels (group_scorer='hip'): one capturable op per sweep iteration.
+    None where the kernels do not apply: the caller keeps its torch closure.
+    Deliberately no score_fn.scoring: the megakernels are single-GP."""
+    if not self._x.is_cuda or self._config.dtype != torch.float32:
+      raise ValueError(
+          "group_scorer='hip' needs a GPU device and dtype float32, got "
+          f'device {self._x.device} and {self._config.dtype}')
+    scoring = acq_lib.GroupScoringFunction(members, a, w, c, acquisition,
+                                           trust_region)
+    if not scoring.applies(self._x):
+      return None
+
+    def score_fn(batch: CandidateBatch) -> torch.Tensor:
+      return scoring(self._codec.decode(batch)[:, 0, :].contiguous())
+    score_fn.graph_safe = True
+    return score_fn
 
   def _qei_hip_score_fn(self, posterior, eps: torch.Tensor,
                         best_value: float, trust_region):

@@ -751,3 +751,73 @@ class ScoringFunction:
     if self.trust_region is not None:
       scores = self.trust_region.apply(xs, scores)
     return scores
+
+
+class GroupScoringFunction:
+  """Several Matern GPs combined into one prediction, as one fused HIP op.
+
+  xs (B, D) -> (B,), GPU and fp32 only. With member predictions (m_g, v_g):
+      mean = sum_g a_g m_g
+      var  = max(sum_g w_g v_g + c sum_g a_g (m_g - mean)^2, 1e-12)
+  then `acquisition` and `trust_region.apply`. a_g = w_g = 1/G and c = 1 is
+  `EnsembleGPPosterior.predict`; a_g = 1, c = 0 and the weights of
+  `StackedResidualGP.levels()` is the transfer-learning stack. Every scalar
+  is hoisted here and every K_inv is symmetrised once, out of place, as
+  0.5 (K_inv + K_inv^T): posterior_score_group.hip reads only the upper tile
+  pairs and needs it exactly symmetric. No host sync per call, so the sweep
+  can capture it in a hipGraph. `applies(xs)` says whether the kernels serve
+  this group; the caller keeps its torch closure where they do not.
+  """
+
+  def __init__(self, members: Sequence[GPPosterior], a: Sequence[float],
+               w: Sequence[float], c: float,
+               acquisition: AcquisitionFunction,
+               trust_region: Optional[TrustRegion] = None):
+    self.members = list(members)
+    self.acquisition = acquisition
+    self.trust_region = trust_region
+    self._a = [float(v) for v in a]
+    self._w = [float(v) for v in w]
+    self._c = float(c)
+    self._acq_name = ScoringFunction._FUSED.get(type(acquisition))
+    self._coef = getattr(acquisition, 'coefficient', 0.0)
+    self._best = getattr(acquisition, 'best_value', 0.0)
+    self._plain = all(type(p) is GPPosterior and p.K_inv is not None
+                      for p in self.members)
+    x0 = self.members[0].x
+    self._tr_anchored = trust_region is None or (
+        trust_region._trusted.shape == x0.shape and
+        trust_region._trusted.data_ptr() == x0.data_ptr())
+    self._tr_radius = (float(trust_region.trust_radius)
+                       if trust_region is not None else 0.0)
+    self._onehot_u8 = (trust_region._onehot.to(torch.uint8)
+                       if trust_region is not None else
+                       torch.zeros(x0.shape[-1], dtype=torch.uint8,
+                                   device=x0.device))
+    if self._plain:
+      ms = self.members
+      self._xs = [p.x.contiguous() for p in ms]
+      self._ls = [p.params.lengthscales.contiguous() for p in ms]
+      self._amps = [float(p.params.amplitude) for p in ms]
+      self._means = [float(p.params.mean) for p in ms]
+      self._alphas = [p.alpha.contiguous() for p in ms]
+      self._ws = [(0.5 * (p.K_inv + p.K_inv.T)).contiguous() for p in ms]
+
+  def operands(self) -> tuple:
+    """The leading arguments of ext.group_scores after xs."""
+    return (self._xs, self._ls, self._amps, self._means, self._alphas,
+            self._ws, self._a, self._w, self._c, self._onehot_u8)
+
+  def applies(self, xs: torch.Tensor) -> bool:
+    return (xs.is_cuda and xs.dtype == torch.float32 and
+            self._acq_name is not None and self._plain and
+            self._tr_anchored and len(self.members) <= 8 and
+            xs.shape[-1] <= 512 and
+            all(p.x.is_cuda and p.x.dtype == torch.float32 and
+                0 < p.x.shape[0] < 4096 for p in self.members))
+
+  def __call__(self, xs: torch.Tensor) -> torch.Tensor:
+    from vizier_amd._src.ops import dispatch as ops
+    return ops.require_ext().group_scores(
+        xs, *self.operands(), ops.ACQ_CODES[self._acq_name], self._coef,
+        self._best, self._tr_radius)

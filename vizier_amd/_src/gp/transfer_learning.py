@@ -66,6 +66,23 @@ class StackedResidualGP:
         num_obs_base=self._base.num_obs, num_obs_top=self._num_obs)
     return combined.mean, combined.stddev
 
+  def levels(self) -> List[Tuple[gp_model.GPPosterior, float]]:
+    """[(posterior, weight)], top first: `predict` unrolled.
+
+    mean = sum_g m_g and var = sum_g weight_g v_g, with weight_0 = 1 and
+    weight_g the product of the dof factors n_base / (n_base + n_top) of
+    `combine_predictions` down the chain (its clamps are no-ops: every v_g
+    is already >= 1e-12 and every weight >= 0).
+    """
+    out, weight, node = [], 1.0, self
+    while node is not None:
+      out.append((node._top, weight))
+      base = node._base
+      if base is not None:
+        weight *= base.num_obs / max(base.num_obs + node.num_obs, 1)
+      node = base
+    return out
+
 
 def train_stacked_gp(datasets: Sequence[Tuple[torch.Tensor, torch.Tensor]],
                      *, num_restarts: int = 4, max_iters: int = 50,

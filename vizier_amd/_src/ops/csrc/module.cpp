@@ -144,6 +144,19 @@ extern "C" void launch_mt_mean_std(
     float* dist_part, float* mean_out, float* sd_out, float* dist_out, int b,
     int n, int d, int m, hipStream_t stream);
 
+// Grouped Matern GP scorer: ensembles and stacks (posterior_score_group.hip).
+extern "C" void grp_layout(int g, const int* n, int* ksum, int* tiles,
+                           int* items);
+extern "C" void launch_grp(
+    const float* xq, const unsigned char* onehot, int g,
+    const float* const* x, const float* const* inv_ls,
+    const float* const* alpha, const float* const* w, const int* n,
+    const float* amp2, const float* mean, const float* a, const float* wt,
+    float c, float* k_ws, float* part, float* mu_part, float* dist_part,
+    float* score, float* mean_out, float* sd_out, float* dist_out, int b,
+    int d, int acq, float coef, float best_value, float tr_radius,
+    hipStream_t stream);
+
 extern "C" void launch_qei_cov(
     const float* t_ws, const float* k_ws, const float* mu_ws,
     const float* xs, const float* inv_ls, float* mean_out, float* cov_out,
@@ -1201,6 +1214,126 @@ std::vector<torch::Tensor> multitask_mean_std(
   return {mean_out, sd_out, dist_out};
 }
 
+// -- Grouped Matern GP scorer (posterior_score_group.hip) -------------------
+
+namespace {
+
+// Checks a group's operands, allocates the workspaces and launches the three
+// kernels. with_score: scores (b,); otherwise (mean, sd, dist). Every check
+// precedes the one launch sequence; no host sync and no H2D copy (the ragged
+// operands ride in the kernel argument), so the chain is stream-capturable.
+std::vector<torch::Tensor> group_run(
+    const char* name, const torch::Tensor& xq,
+    const std::vector<torch::Tensor>& xs,
+    const std::vector<torch::Tensor>& ls, const std::vector<double>& amps,
+    const std::vector<double>& means,
+    const std::vector<torch::Tensor>& alphas,
+    const std::vector<torch::Tensor>& ws, const std::vector<double>& a,
+    const std::vector<double>& w, double c, const torch::Tensor& onehot,
+    bool with_score, int acq, double coef, double best, double tr_radius) {
+  const size_t g = xs.size();
+  TORCH_CHECK(g >= 1 && g <= 8, name, " supports 1 <= G <= 8 members, got ",
+              g);
+  TORCH_CHECK(ls.size() == g && amps.size() == g && means.size() == g &&
+              alphas.size() == g && ws.size() == g && a.size() == g &&
+              w.size() == g, name, ": every per-member list must have ", g,
+              " entries");
+  auto fp32_gpu = [&](const torch::Tensor& t) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                t.is_contiguous(), name,
+                " takes contiguous fp32 GPU tensors");
+  };
+  fp32_gpu(xq);
+  TORCH_CHECK(xq.dim() == 2 && xq.size(0) >= 1 && xq.size(1) >= 1,
+              "xq must be (b >= 1, D >= 1)");
+  const int64_t b = xq.size(0), d = xq.size(1);
+  TORCH_CHECK(d <= 512, name, " supports D <= 512, got ", d);
+  TORCH_CHECK(onehot.scalar_type() == torch::kUInt8 && onehot.is_cuda() &&
+              onehot.is_contiguous() && onehot.numel() == d,
+              "onehot must be a contiguous uint8 GPU tensor of ", d,
+              " elements");
+  int n[8];
+  float amp2[8], mean[8], af[8], wf[8];
+  for (size_t i = 0; i < g; ++i) {
+    for (const auto* t : {&xs[i], &ls[i], &alphas[i], &ws[i]}) fp32_gpu(*t);
+    TORCH_CHECK(xs[i].dim() == 2 && xs[i].size(1) == d, "x[", i,
+                "] must have xq's ", d, " columns");
+    const int64_t ni = xs[i].size(0);
+    TORCH_CHECK(ni >= 1 && ni < 4096, name, " supports 1 <= N < 4096, got ",
+                ni, " for member ", i);
+    TORCH_CHECK(ls[i].numel() == d, "ls[", i, "] must have ", d,
+                " elements");
+    TORCH_CHECK(alphas[i].numel() == ni, "alpha[", i, "] must have ", ni,
+                " elements");
+    TORCH_CHECK(ws[i].dim() == 2 && ws[i].size(0) == ni &&
+                ws[i].size(1) == ni, "w[", i, "] must be (", ni, ", ", ni,
+                ")");
+    n[i] = (int)ni;
+    amp2[i] = (float)(amps[i] * amps[i]);
+    mean[i] = (float)means[i];
+    af[i] = (float)a[i];
+    wf[i] = (float)w[i];
+  }
+  int ksum, tiles, items;
+  grp_layout((int)g, n, &ksum, &tiles, &items);
+  TORCH_CHECK(b * ksum < (int64_t{1} << 31) &&
+              b * items < (int64_t{1} << 31), name,
+              ": the workspace is too large");
+  auto inv_ls = torch::stack(ls).reciprocal();  // (G, D)
+  const auto opt = xq.options();
+  auto k_ws = torch::empty({b, ksum}, opt);
+  auto part = torch::empty({b, items}, opt);
+  auto mu_part = torch::empty({b, tiles}, opt);
+  auto dist_part = torch::empty({b, (n[0] + 63) / 64}, opt);
+  std::vector<torch::Tensor> out;
+  for (int i = 0; i < (with_score ? 1 : 3); ++i) {
+    out.push_back(torch::empty({b}, opt));
+  }
+  const float *xp[8], *ilp[8], *ap[8], *wp[8];
+  for (size_t i = 0; i < g; ++i) {
+    xp[i] = xs[i].data_ptr<float>();
+    ilp[i] = inv_ls.data_ptr<float>() + i * d;
+    ap[i] = alphas[i].data_ptr<float>();
+    wp[i] = ws[i].data_ptr<float>();
+  }
+  launch_grp(
+      xq.data_ptr<float>(), onehot.data_ptr<unsigned char>(), (int)g, xp, ilp,
+      ap, wp, n, amp2, mean, af, wf, (float)c, k_ws.data_ptr<float>(),
+      part.data_ptr<float>(), mu_part.data_ptr<float>(),
+      dist_part.data_ptr<float>(),
+      with_score ? out[0].data_ptr<float>() : nullptr,
+      with_score ? nullptr : out[0].data_ptr<float>(),
+      with_score ? nullptr : out[1].data_ptr<float>(),
+      with_score ? nullptr : out[2].data_ptr<float>(), (int)b, (int)d, acq,
+      (float)coef, (float)best, (float)tr_radius, current_stream());
+  return out;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> group_mean_std(
+    torch::Tensor xq, std::vector<torch::Tensor> xs,
+    std::vector<torch::Tensor> ls, std::vector<double> amps,
+    std::vector<double> means, std::vector<torch::Tensor> alphas,
+    std::vector<torch::Tensor> ws, std::vector<double> a,
+    std::vector<double> w, double c, torch::Tensor onehot) {
+  return group_run("group_mean_std", xq, xs, ls, amps, means, alphas, ws, a,
+                   w, c, onehot, false, 0, 0.0, 0.0, 0.0);
+}
+
+torch::Tensor group_scores(
+    torch::Tensor xq, std::vector<torch::Tensor> xs,
+    std::vector<torch::Tensor> ls, std::vector<double> amps,
+    std::vector<double> means, std::vector<torch::Tensor> alphas,
+    std::vector<torch::Tensor> ws, std::vector<double> a,
+    std::vector<double> w, double c, torch::Tensor onehot, int64_t acq,
+    double coef, double best, double tr_radius) {
+  TORCH_CHECK(acq >= 0 && acq <= 3, "group_scores supports UCB, LCB, EI and "
+              "PI (codes 0..3), got ", acq);
+  return group_run("group_scores", xq, xs, ls, amps, means, alphas, ws, a, w,
+                   c, onehot, true, (int)acq, coef, best, tr_radius)[0];
+}
+
 // -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
 
 namespace {
@@ -2090,6 +2223,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Matern + linear kernel (mean, sd, min-Linf dist) (gfx950)");
   m.def("multitask_mean_std", &multitask_mean_std,
         "Separable multitask GP (means, sds, min-Linf dist) (gfx950)");
+  m.def("group_mean_std", &group_mean_std,
+        "Group of G <= 8 Matern GPs (ensemble mixture or transfer stack): "
+        "(mean, sd, min-Linf dist to member 0's x). Every ws[g] must be "
+        "EXACTLY symmetric: only its upper tile pairs are read (gfx950)");
+  m.def("group_scores", &group_scores,
+        "group_mean_std + acquisition + trust region in one capturable op. "
+        "Every ws[g] must be EXACTLY symmetric (gfx950)");
   m.def("posterior_scores_chunked", &posterior_scores_chunked,
         "3-kernel chunked GP posterior scorer (chip-filling, gfx950)");
   m.def("qei_joint_mean_cov", &qei_joint_mean_cov,

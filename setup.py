@@ -21,6 +21,7 @@ _SRC = [
     'vizier_amd/_src/ops/csrc/posterior_score_linear.hip',
     'vizier_amd/_src/ops/csrc/posterior_score_multitask.hip',
     'vizier_amd/_src/ops/csrc/posterior_score_group.hip',
+    'vizier_amd/_src/ops/csrc/posterior_score_pe.hip',
     'vizier_amd/_src/ops/csrc/qei_score.hip',
     'vizier_amd/_src/ops/csrc/setpe_score.hip',
     'vizier_amd/_src/ops/csrc/batched_chol.hip',

@@ -86,6 +86,18 @@ class UCBPEConfig:
   # land on the other side of "pivot > 0" and suggestions can differ from
   # 'torch'.
   set_pe_scorer: str = 'torch'
+  # Scorer of the single-metric single-point sweeps that are conditioned on
+  # pending rows (active trials and batch members already chosen): 'torch'
+  # (default: today's closures) or 'hip' (opt-in, GPU + float32 only: the
+  # fused posterior_score_pe.hip scorer, one k-vector over completed +
+  # pending rows for both posteriors, captured in a hipGraph). 'hip' serves
+  # the PE member and the UCB member whose trust region holds pending rows;
+  # the UCB member without pending rows keeps the pure-HIP scorer and the
+  # megakernel. Multimetric studies, the linear kernel, ensembles and shapes
+  # beyond the kernels' limits keep today's closures. The captured sweep
+  # selects from the final pool and the fp32 sums run in another order, so
+  # suggestions can differ from 'torch'.
+  pe_scorer: str = 'torch'
   max_evaluations: int = 75000
   suggestion_batch_size: int = 25
   num_seed_trials: int = 2
@@ -108,6 +120,9 @@ class VizierGPUCBPEBandit(Designer):
     if self._config.set_pe_scorer not in ('torch', 'hip'):
       raise ValueError("set_pe_scorer must be 'torch' or 'hip', got "
                        f'{self._config.set_pe_scorer!r}')
+    if self._config.pe_scorer not in ('torch', 'hip'):
+      raise ValueError("pe_scorer must be 'torch' or 'hip', got "
+                       f'{self._config.pe_scorer!r}')
     if self._config.multitask_scorer not in ('torch', 'hip'):
       raise ValueError("multitask_scorer must be 'torch' or 'hip', got "
                        f'{self._config.multitask_scorer!r}')
@@ -484,6 +499,24 @@ class VizierGPUCBPEBandit(Designer):
             post.x.dtype == torch.float32 and
             (x_all is None or post.x.data_ptr() == x_all.data_ptr()))
 
+  def _pe_hip_score_fn(self, posterior, x_all, var_post, trust_region,
+                       **coefs):
+    """pe_scorer='hip': the capturable closure decode ->
+    acq_lib.PEScoringFunction (UCB without var_post, PE with it), or None
+    where the knob is off or the kernels do not serve the case."""
+    if (self._config.pe_scorer != 'hip' or
+        type(posterior) is not gp_model.GPPosterior):
+      return None
+    scoring = acq_lib.PEScoringFunction(posterior, x_all, var_post,
+                                        trust_region, **coefs)
+    if not scoring.applies(x_all):
+      return None
+
+    def score_fn(batch: CandidateBatch) -> torch.Tensor:
+      return scoring(self._codec.decode(batch)[:, 0, :])
+    score_fn.graph_safe = True
+    return score_fn
+
   def _tr_kernel_args(self, trust_region, device):
     onehot = (trust_region._onehot.to(torch.uint8)
               if trust_region is not None else torch.zeros(
@@ -537,6 +570,11 @@ class VizierGPUCBPEBandit(Designer):
     posterior = self._posterior
     trust_region = acq_lib.TrustRegion.for_converter(
         x_all, self._converter) if cfg.use_trust_region else None
+    if cfg.pe_scorer == 'hip' and (
+        not x_all.is_cuda or cfg.dtype != torch.float32):
+      raise ValueError(
+          "pe_scorer='hip' needs a GPU device and dtype float32, got "
+          f'device {x_all.device} and {cfg.dtype}')
 
     if self._mo_posteriors is not None:
       posts = self._mo_posteriors
@@ -683,6 +721,13 @@ class VizierGPUCBPEBandit(Designer):
         # the codec's column maps.
         score_fn.codec = self._codec
       else:
+        hip_fn = self._pe_hip_score_fn(
+            posterior, x_all, None, trust_region,
+            coef=cfg.ucb_coefficient)
+        if hip_fn is not None:
+          # pe_scorer='hip': the distance runs over all rows of x_all, the
+          # mean and variance over the fitted rows, in one capturable op.
+          return hip_fn
         # Pending points anchor the trust region elsewhere: composed
         # rocBLAS path, not capturable on this ROCm build.
         score_fn.graph_safe = False  # float(tensor) syncs in predict
@@ -693,6 +738,14 @@ class VizierGPUCBPEBandit(Designer):
       ucb_obs = mean_obs + cfg.ucb_coefficient * stddev_obs
       threshold = mean_obs[int(torch.argmax(ucb_obs))]
       var_post = self._variance_posterior(x_all)
+
+      hip_fn = self._pe_hip_score_fn(
+          posterior, x_all, var_post, trust_region,
+          explore_coef=cfg.explore_region_ucb_coefficient,
+          threshold=float(threshold),
+          penalty_coef=cfg.cb_violation_penalty_coefficient)
+      if hip_fn is not None:
+        return hip_fn
 
       if (cfg.dtype == torch.float32 and self._fusable(posterior) and
           self._fusable(var_post, x_all)):

@@ -547,6 +547,80 @@ class SetPEScoringFunction:
         self._penalty_coef, self._tr_radius)
 
 
+class PEScoringFunction:
+  """GP-UCB-PE's single-point score on completed + pending rows, one HIP op.
+
+  xs (B, D) -> (B,), GPU and fp32 only. `x_all` holds `posterior.x` first,
+  then the pending and already chosen rows. Without `var_posterior` (UCB):
+      mean + coef * stddev
+  with it (PE; the posterior conditioned on all of x_all, variance only):
+      stddev_all + penalty_coef * min(mean + explore_coef * stddev
+                                      - threshold, 0)
+  then the trust region over ALL rows of x_all. Both posteriors share the
+  hyperparameters, so posterior_score_pe.hip computes one k-vector over x_all
+  and reads the fitted posterior's out of its first N entries. Every scalar is
+  hoisted here and each K_inv is symmetrised once, out of place, as
+  0.5 (K_inv + K_inv^T): the kernel reads only the upper tile pairs, and
+  z.T @ z carries no symmetry guarantee. No host sync per call, so the sweep
+  can capture it in a hipGraph. `applies(xs)` says whether the kernels serve
+  this case; the caller keeps its own closure where they do not.
+  """
+
+  def __init__(self, posterior: GPPosterior, x_all: torch.Tensor,
+               var_posterior: Optional[GPPosterior] = None,
+               trust_region: Optional[TrustRegion] = None, *,
+               coef: float = 0.0, explore_coef: float = 0.0,
+               threshold: float = 0.0, penalty_coef: float = 0.0):
+    self.posterior = posterior
+    self.var_posterior = var_posterior
+    self.trust_region = trust_region
+    self._x_all = x_all
+    n = posterior.x.shape[0]
+    self._plain = (
+        type(posterior) is GPPosterior and posterior.K_inv is not None and
+        x_all.dim() == 2 and n <= x_all.shape[0] and
+        x_all.dtype == posterior.x.dtype and
+        (x_all.data_ptr() == posterior.x.data_ptr() or
+         torch.equal(x_all[:n], posterior.x)))
+    if var_posterior is not None:
+      self._plain = (
+          self._plain and type(var_posterior) is GPPosterior and
+          var_posterior.K_inv is not None and
+          var_posterior.params is posterior.params and
+          var_posterior.x is x_all)
+    self._tr_anchored = trust_region is None or (
+        trust_region._trusted.shape == x_all.shape and
+        trust_region._trusted.data_ptr() == x_all.data_ptr())
+    self._tr_radius = (float(trust_region.trust_radius)
+                       if trust_region is not None else 0.0)
+    self._onehot_u8 = (trust_region._onehot.to(torch.uint8)
+                       if trust_region is not None else
+                       torch.zeros(x_all.shape[-1], dtype=torch.uint8,
+                                   device=x_all.device))
+    self._mode = 0 if var_posterior is None else 1
+    self._tail = (float(coef), float(explore_coef), float(threshold),
+                  float(penalty_coef), self._tr_radius)
+    if self._plain:
+      sym = lambda m: (0.5 * (m + m.T)).contiguous()
+      self._operands = (
+          x_all.contiguous(), posterior.params.lengthscales.contiguous(),
+          float(posterior.params.amplitude), float(posterior.params.mean),
+          posterior.alpha.contiguous(), sym(posterior.K_inv),
+          sym(var_posterior.K_inv) if var_posterior is not None else None,
+          self._onehot_u8)
+
+  def applies(self, xs: torch.Tensor) -> bool:
+    return (xs.is_cuda and xs.dtype == torch.float32 and self._plain and
+            self._tr_anchored and self._x_all.is_cuda and
+            self._x_all.dtype == torch.float32 and xs.shape[-1] <= 512 and
+            0 < self._x_all.shape[0] < 4096)
+
+  def __call__(self, xs: torch.Tensor) -> torch.Tensor:
+    from vizier_amd._src.ops import dispatch as ops
+    return ops.require_ext().pe_scores(xs, *self._operands, self._mode,
+                                       *self._tail)
+
+
 class ScoringFunction:
   """Posterior + acquisition + optional trust region, over a batch.
 

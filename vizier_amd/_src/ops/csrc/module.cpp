@@ -157,6 +157,18 @@ extern "C" void launch_grp(
     int d, int acq, float coef, float best_value, float tr_radius,
     hipStream_t stream);
 
+// GP-UCB-PE scorer conditioned on pending points (posterior_score_pe.hip).
+extern "C" void pe_layout(int na, int n_fit, int with_all, int* tiles,
+                          int* items_fit, int* items);
+extern "C" void launch_pe(
+    const float* xq, const float* x, const float* inv_ls, const float* alpha,
+    const float* w_fit, const float* w_all, const unsigned char* onehot,
+    float* k_ws, float* part, float* mu_part, float* dist_part, float* score,
+    float* mean_out, float* sd_out, float* sd_all_out, float* dist_out, int b,
+    int na, int n_fit, int d, float amp2, float mean_c, float coef,
+    float explore_coef, float threshold, float pen_coef, float tr_radius,
+    hipStream_t stream);
+
 extern "C" void launch_qei_cov(
     const float* t_ws, const float* k_ws, const float* mu_ws,
     const float* xs, const float* inv_ls, float* mean_out, float* cov_out,
@@ -1334,6 +1346,112 @@ torch::Tensor group_scores(
                    c, onehot, true, (int)acq, coef, best, tr_radius)[0];
 }
 
+// -- GP-UCB-PE scorer conditioned on pending points (posterior_score_pe.hip) -
+
+namespace {
+
+// Checks the operands, allocates the workspaces and launches the three
+// kernels. w_all undefined is UCB mode. with_score: scores (b,); otherwise
+// (mean, sd, sd_all, dist), sd_all empty in UCB mode. Every check precedes
+// the one launch sequence; no host sync, so the chain is stream-capturable.
+std::vector<torch::Tensor> pe_run(
+    const char* name, const torch::Tensor& xq, const torch::Tensor& x_all,
+    const torch::Tensor& ls, double amp, double mean_c,
+    const torch::Tensor& alpha, const torch::Tensor& w_fit,
+    const torch::Tensor& w_all, const torch::Tensor& onehot, bool with_score,
+    double coef, double explore_coef, double threshold, double pen_coef,
+    double tr_radius) {
+  const bool pe = w_all.defined();
+  for (const auto* t : {&xq, &x_all, &ls, &alpha, &w_fit, &w_all}) {
+    TORCH_CHECK(!t->defined() ||
+                (t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                 t->is_contiguous()), name,
+                " takes contiguous fp32 GPU tensors");
+  }
+  TORCH_CHECK(xq.dim() == 2 && x_all.dim() == 2, "xq and x_all must be 2-D");
+  const int64_t b = xq.size(0), d = xq.size(1), na = x_all.size(0);
+  const int64_t n_fit = alpha.numel();
+  TORCH_CHECK(x_all.size(1) == d, "x_all must have xq's ", d,
+              " columns, got ", x_all.size(1));
+  TORCH_CHECK(b >= 1 && d >= 1 && n_fit >= 1, name, " needs at least one "
+              "candidate, column and fitted row");
+  TORCH_CHECK(d <= 512, name, " supports D <= 512, got ", d);
+  TORCH_CHECK(na < 4096, name, " supports Na < 4096, got ", na);
+  TORCH_CHECK(n_fit <= na, "alpha has ", n_fit, " entries but x_all only ",
+              na, " rows");
+  TORCH_CHECK(alpha.dim() == 1, "alpha must be 1-D");
+  TORCH_CHECK(w_fit.dim() == 2 && w_fit.size(0) == n_fit &&
+              w_fit.size(1) == n_fit, "w_fit must be (", n_fit, ", ", n_fit,
+              ")");
+  TORCH_CHECK(!pe || (w_all.dim() == 2 && w_all.size(0) == na &&
+                      w_all.size(1) == na), "w_all must be (", na, ", ", na,
+              ")");
+  TORCH_CHECK(ls.numel() == d, "ls must have ", d, " elements");
+  TORCH_CHECK(onehot.scalar_type() == torch::kUInt8 && onehot.is_cuda() &&
+              onehot.is_contiguous() && onehot.numel() == d,
+              "onehot must be a contiguous uint8 GPU tensor of ", d,
+              " elements");
+  int tiles, items_fit, items;
+  pe_layout((int)na, (int)n_fit, pe, &tiles, &items_fit, &items);
+  TORCH_CHECK(b * na < (int64_t{1} << 31) && b * items < (int64_t{1} << 31),
+              name, ": the workspace is too large");
+  auto inv_ls = ls.reciprocal();
+  const auto opt = xq.options();
+  auto k_ws = torch::empty({b, na}, opt);
+  auto part = torch::empty({b, items}, opt);
+  auto mu_part = torch::empty({b, tiles}, opt);
+  auto dist_part = torch::empty({b, tiles}, opt);
+  std::vector<torch::Tensor> out;
+  if (with_score) {
+    out = {torch::empty({b}, opt)};
+  } else {
+    out = {torch::empty({b}, opt), torch::empty({b}, opt),
+           torch::empty({pe ? b : 0}, opt), torch::empty({b}, opt)};
+  }
+  auto ptr = [&](int i) {
+    return with_score ? nullptr : out[i].data_ptr<float>();
+  };
+  launch_pe(
+      xq.data_ptr<float>(), x_all.data_ptr<float>(),
+      inv_ls.data_ptr<float>(), alpha.data_ptr<float>(),
+      w_fit.data_ptr<float>(), pe ? w_all.data_ptr<float>() : nullptr,
+      onehot.data_ptr<unsigned char>(), k_ws.data_ptr<float>(),
+      part.data_ptr<float>(), mu_part.data_ptr<float>(),
+      dist_part.data_ptr<float>(),
+      with_score ? out[0].data_ptr<float>() : nullptr, ptr(0), ptr(1),
+      ptr(2), ptr(3), (int)b, (int)na, (int)n_fit, (int)d,
+      (float)(amp * amp), (float)mean_c, (float)coef, (float)explore_coef,
+      (float)threshold, (float)pen_coef, (float)tr_radius, current_stream());
+  return out;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> pe_mean_std(
+    torch::Tensor xq, torch::Tensor x_all, torch::Tensor ls, double amp,
+    double mean_c, torch::Tensor alpha, torch::Tensor w_fit,
+    c10::optional<torch::Tensor> w_all, torch::Tensor onehot) {
+  return pe_run("pe_mean_std", xq, x_all, ls, amp, mean_c, alpha, w_fit,
+                w_all.value_or(torch::Tensor()), onehot, false, 0.0, 0.0,
+                0.0, 0.0, 0.0);
+}
+
+// mode 0: UCB, w_all must be None; mode 1: PE, w_all must be given.
+torch::Tensor pe_scores(
+    torch::Tensor xq, torch::Tensor x_all, torch::Tensor ls, double amp,
+    double mean_c, torch::Tensor alpha, torch::Tensor w_fit,
+    c10::optional<torch::Tensor> w_all, torch::Tensor onehot, int64_t mode,
+    double coef, double explore_coef, double threshold, double pen_coef,
+    double tr_radius) {
+  TORCH_CHECK(mode == 0 || mode == 1, "pe_scores takes mode 0 (UCB) or 1 "
+              "(PE), got ", mode);
+  TORCH_CHECK(w_all.has_value() == (mode == 1), "pe_scores takes w_all in "
+              "PE mode (1) and None in UCB mode (0)");
+  return pe_run("pe_scores", xq, x_all, ls, amp, mean_c, alpha, w_fit,
+                w_all.value_or(torch::Tensor()), onehot, true, coef,
+                explore_coef, threshold, pen_coef, tr_radius)[0];
+}
+
 // -- Set-PE logdet scorer of GP-UCB-PE (setpe_score.hip) -------------------
 
 namespace {
@@ -2230,6 +2348,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_scores", &group_scores,
         "group_mean_std + acquisition + trust region in one capturable op. "
         "Every ws[g] must be EXACTLY symmetric (gfx950)");
+  m.def("pe_mean_std", &pe_mean_std,
+        "GP-UCB-PE scorer on x_all = fitted rows + pending rows: (mean, sd, "
+        "sd_all, min-Linf dist to ALL rows) from one k-vector; w_all None "
+        "is UCB mode (sd_all empty). w_fit and w_all must be EXACTLY "
+        "symmetric: only their upper tile pairs are read (gfx950)");
+  m.def("pe_scores", &pe_scores,
+        "pe_mean_std + UCB (mode 0) or PE (mode 1) + trust region in one "
+        "capturable op. w_fit and w_all must be EXACTLY symmetric (gfx950)");
   m.def("posterior_scores_chunked", &posterior_scores_chunked,
         "3-kernel chunked GP posterior scorer (chip-filling, gfx950)");
   m.def("qei_joint_mean_cov", &qei_joint_mean_cov,

@@ -28,6 +28,7 @@ _SRC = [
     'vizier_amd/_src/ops/csrc/eagle_step.hip',
     'vizier_amd/_src/ops/csrc/eagle_sweep.hip',
     'vizier_amd/_src/ops/csrc/eagle_sweep_mixed.hip',
+    'vizier_amd/_src/ops/csrc/eagle_sweep_mo.hip',
     'vizier_amd/_src/ops/csrc/posterior_score_f64.hip',
     'vizier_amd/_src/ops/csrc/gram_matern52_f64.hip',
 ]

@@ -36,6 +36,7 @@ from vizier_amd._src.algorithms.optimizers.eagle import (
 )
 from vizier_amd._src.algorithms.optimizers.vectorized import (
     EagleFeatureCodec,
+    MoSweepScoring,
     VectorizedOptimizerFactory,
     trials_to_sorted_features,
 )
@@ -641,6 +642,14 @@ class VizierGPUCBPEBandit(Designer):
                 dist if trust_region is not None else None,
                 cfg.ucb_coefficient, tr_radius)
           score_fn.graph_safe = True
+          if self._codec.identity:
+            # The sweep megakernel's operands (eagle_sweep_mo.hip).
+            mo = MoSweepScoring.build(
+                posts, post_amps, post_means, weights, ref, onehot,
+                cfg.ucb_coefficient, tr_radius)
+            if mo is not None:
+              score_fn.mo_scoring = mo
+              score_fn.codec_identity = True
         else:
           def score_fn(batch: CandidateBatch) -> torch.Tensor:
             xs = self._codec.decode(batch)[:, 0, :]

@@ -35,6 +35,51 @@ class VectorizedStrategyResults:
   rewards: torch.Tensor             # (count,)
 
 
+@dataclasses.dataclass
+class MoSweepScoring:
+  """What the multi-objective sweep megakernel (eagle_sweep_mo.hip) needs
+  of a fused multi-objective score closure: M Matern GPs on one training
+  set and the hypervolume scalarisation, every operand built once per
+  suggest. A designer attaches it to its closure as `score_fn.mo_scoring`;
+  the closure itself (the hipGraph path) is unchanged."""
+
+  x: torch.Tensor                 # (N, D), shared by the M posteriors
+  inv_ls: torch.Tensor            # (M, D)
+  alpha: torch.Tensor             # (M, N)
+  k_invs: List[torch.Tensor]      # M x (N, N), the posteriors' own tensors
+  amp2: List[float]               # amplitude^2 per metric
+  mean_c: List[float]
+  weights: torch.Tensor           # (S, M)
+  ref: Optional[torch.Tensor]     # (M,) or None
+  onehot: torch.Tensor            # (D,) uint8 trust-region column mask
+  coef: float
+  tr_radius: float                # 0: no trust region
+
+  @classmethod
+  def build(cls, posts, amps, mean_cs, weights, ref, onehot, coef,
+            tr_radius) -> Optional['MoSweepScoring']:
+    """None where the posteriors are not M fp32 GPs on one training set
+    (the kernel makes one pass over x for all metrics)."""
+    x = posts[0].x
+    for p in posts:
+      if (p.K_inv is None or not p.K_inv.is_contiguous() or
+          p.K_inv.dtype != torch.float32 or p.x.dtype != torch.float32 or
+          p.x.shape != x.shape or
+          not (p.x.data_ptr() == x.data_ptr() or torch.equal(p.x, x))):
+        return None
+    # 1 / lengthscales in fp32 and amp * amp in double, as
+    # posterior_mean_std forms them: the sweep is bit-equal to that path.
+    return cls(
+        x=x.contiguous(),
+        inv_ls=torch.stack(
+            [1.0 / p.params.lengthscales for p in posts]).contiguous(),
+        alpha=torch.stack([p.alpha for p in posts]).contiguous(),
+        k_invs=[p.K_inv for p in posts],
+        amp2=[a * a for a in amps], mean_c=list(mean_cs), weights=weights,
+        ref=ref, onehot=onehot.contiguous(), coef=float(coef),
+        tr_radius=float(tr_radius))
+
+
 class VectorizedOptimizer:
   """Runs a vectorized strategy against a batched score function."""
 
@@ -135,8 +180,11 @@ class VectorizedOptimizer:
       return False
     strategy = self.strategy
     scoring = getattr(score_fn, 'scoring', None)
-    if strategy._ext is None or scoring is None:
+    if strategy._ext is None:
       return False
+    if scoring is None:
+      # Several metrics: a fused closure carries mo_scoring instead.
+      return self._megakernel_mo_applicable(score_fn)
     if not getattr(score_fn, 'codec_identity', False):
       return self._megakernel_mixed_applicable(score_fn)
     if strategy.categorical_sizes or strategy.n_parallel != 1:
@@ -194,6 +242,32 @@ class VectorizedOptimizer:
             list(codec.categorical_sizes) == strategy.categorical_sizes and
             post.x.shape[0] < 4096)
 
+  def _megakernel_mo_applicable(self, score_fn: ScoreFn) -> bool:
+    """Preconditions of the multi-objective megakernel
+    (eagle_sweep_mo.hip): a fused multi-objective closure (mo_scoring: 2
+    to 4 fp32 Matern GPs on one training set), a continuous space, q == 1,
+    the pool within the resident cap and N < 4096, where the standalone
+    scorer takes the same tile quadform and the suggestions are
+    bit-identical to the hipGraph path's. VIZIER_AMD_MEGAKERNEL_MO=0 forces
+    the hipGraph path for multi-objective sweeps only."""
+    import os
+    if os.environ.get('VIZIER_AMD_MEGAKERNEL_MO', '1') != '1':
+      return False
+    strategy = self.strategy
+    mo = getattr(score_fn, 'mo_scoring', None)
+    if (mo is None or strategy._ext is None or
+        not hasattr(strategy._ext, 'eagle_sweep_mo') or
+        strategy.categorical_sizes or strategy.n_parallel != 1 or
+        strategy.dtype != torch.float32):
+      return False
+    pool, n, d = strategy.pool_size, mo.x.shape[0], mo.x.shape[1]
+    return (2 <= len(mo.k_invs) <= 4 and mo.x.is_cuda and
+            pool <= 128 and strategy.batch_size <= 32 and
+            pool % strategy.batch_size == 0 and
+            d == strategy.n_continuous and d <= 512 and
+            pool * d <= self._RESIDENT_CAP and 1 <= n < 4096 and
+            mo.weights.shape[0] >= 1)
+
   def _optimize_megakernel(self, score_fn: ScoreFn, count: int, state,
                            iterations: int) -> VectorizedStrategyResults:
     """Runs the steady-state sweep inside ONE cooperatively-launched
@@ -209,8 +283,10 @@ class VectorizedOptimizer:
     import torch as _torch
 
     strategy = self.strategy
-    scoring = score_fn.scoring
-    post = scoring.posterior
+    scoring = getattr(score_fn, 'scoring', None)
+    # Several metrics (eagle_sweep_mo.hip): mo_scoring stands in.
+    mo = score_fn.mo_scoring if scoring is None else None
+    post = scoring.posterior if mo is None else None
     cfg = strategy.config
     n_batches = strategy.pool_size // strategy.batch_size
 
@@ -222,7 +298,27 @@ class VectorizedOptimizer:
       strategy.update(state, batch, rewards)
     remaining = iterations - eager_iters
 
-    if remaining > 0:
+    if remaining > 0 and mo is not None:
+      b, m = strategy.batch_size, len(mo.k_invs)
+      n, dev = mo.x.shape[0], mo.x.device
+      tiles_n = (n + 63) // 64
+
+      def ws(*shape):
+        return _torch.empty(*shape, dtype=_torch.float32, device=dev)
+      strategy._ext.eagle_sweep_mo(
+          state.continuous, state.rewards, state.perturbations,
+          state.best_reward.reshape(1), strategy._iter_t,
+          _torch.zeros(2, dtype=_torch.int32, device=dev), mo.x, mo.inv_ls,
+          mo.alpha, mo.k_invs, mo.amp2, mo.mean_c, mo.weights, mo.ref,
+          mo.onehot, strategy._out_cont, ws(m, b, n), ws(m, b), ws(b),
+          ws(m, b, tiles_n * tiles_n + 1), ws(2, m, b), ws(b),
+          n_batches, b, strategy.pool_size, state.iterations, remaining,
+          cfg.visibility, cfg.gravity, cfg.negative_gravity,
+          cfg.normalization_scale, cfg.penalize_factor,
+          cfg.perturbation_lower_bound, cfg.perturbation, strategy._seed,
+          strategy._seed ^ 0xABCDEF, mo.coef, mo.tr_radius)
+      state.iterations += remaining
+    elif remaining > 0:
       b = strategy.batch_size
       n = post.x.shape[0]
       dev = post.x.device

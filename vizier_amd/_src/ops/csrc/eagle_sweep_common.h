@@ -1,6 +1,7 @@
 // Device helpers shared by the persistent sweep megakernels:
-// eagle_sweep.hip (continuous spaces) and eagle_sweep_mixed.hip (mixed
-// categorical + continuous spaces). Both kernels have the same workgroup
+// eagle_sweep.hip (continuous spaces), eagle_sweep_mixed.hip (mixed
+// categorical + continuous spaces) and eagle_sweep_mo.hip (several metrics,
+// continuous spaces). The kernels have the same workgroup
 // shape, the same grid barrier, the same block reductions and the same
 // 64x64 tile quadform, so their phases B / B2 and the reduce of C / RC are
 // one text. See the header of eagle_sweep.hip for the design.
@@ -158,9 +159,14 @@ __device__ __forceinline__ void sweep_block_reduce2(
 // __syncthreads, fold_quad(wp, q) is bit for bit what B2 stores. The loads
 // of a trip are issued together (rows past the batch re-read its last
 // row, so the unrolled loop has no branch that would wait per candidate).
-__device__ __forceinline__ void reduce_all_partials(
-    const float* var_ws, int batch_size, int total_tiles, float* wp) {
-  const int tid = threadIdx.x;
+//
+// `tid` is the thread's index among the BLOCK threads that reduce: the
+// continuous and the mixed kernel reduce on half 0 (reduce_all_partials,
+// tid = threadIdx.x); the multi-objective kernel gives each half a metric
+// (eagle_sweep_mo.hip, tid = threadIdx.x % BLOCK).
+__device__ __forceinline__ void reduce_all_partials_at(
+    const float* var_ws, int batch_size, int total_tiles, float* wp,
+    const int tid) {
   float sacc[VZ_QF_QMAX];
 #pragma unroll
   for (int q = 0; q < VZ_QF_QMAX; ++q) sacc[q] = 0.0f;
@@ -205,6 +211,11 @@ __device__ __forceinline__ void reduce_all_partials(
     const int q = (int)(__brev((unsigned)(lane >> 1)) >> 27);
     wp[(tid / WAVE_SIZE) * VZ_QF_QMAX + q] = total;
   }
+}
+
+__device__ __forceinline__ void reduce_all_partials(
+    const float* var_ws, int batch_size, int total_tiles, float* wp) {
+  reduce_all_partials_at(var_ws, batch_size, total_tiles, wp, threadIdx.x);
 }
 
 // block_reduce's second stage over the 4 wave partials: lanes 0..3 hold

@@ -234,6 +234,22 @@ extern "C" int launch_eagle_sweep_mixed(
     unsigned long long seed_update, float amp2, float mean_c, int acq,
     float coef, float best_value, float tr_radius, hipStream_t stream);
 
+extern "C" int launch_eagle_sweep_mo(
+    float* pool_cont, float* rewards, float* perturbations,
+    float* best_reward, unsigned long long* iter_ptr,
+    unsigned int* barrier_buf, const float* x, const float* inv_ls,
+    const float* alpha, const float* const* kinv, const float* amp2,
+    const float* mean_c, const float* weights, const float* ref,
+    const unsigned char* tr_mask, float* out_cont, float* k_ws, float* mu_ws,
+    float* dist_ws, float* var_ws, float* ms_ws, float* score_ws,
+    float* slot_ws, int m, int n_batches, int batch_size, int pool_size,
+    int dc, int n, int n_scal, long long it_start, long long iterations,
+    float visibility, float gravity, float neg_gravity, float norm_scale,
+    float penalize_factor, float perturbation_lower_bound,
+    float base_perturbation, unsigned long long seed_suggest,
+    unsigned long long seed_update, float coef, float tr_radius,
+    hipStream_t stream);
+
 extern "C" void launch_eagle_update(
     float* pool_cont, long* pool_cat, float* rewards, float* perturbations,
     const float* batch_cont, const long* batch_cat,
@@ -2188,6 +2204,158 @@ int64_t eagle_sweep_mixed(
   return ret;
 }
 
+// The multi-objective sweep (eagle_sweep_mo.hip): M Matern GPs on one
+// training set, hypervolume scalarisation, continuous space. kinv is one
+// (N, N) tensor per metric, so nothing is stacked or copied per call;
+// amp2 and mean_c are per-metric host scalars, rounded to fp32 as
+// posterior_mean_std rounds them. ms_ws (2, M, B) receives the kernel's
+// mean and sd, score_ws (B,) its scores.
+int64_t eagle_sweep_mo(
+    torch::Tensor pool_cont, torch::Tensor rewards,
+    torch::Tensor perturbations, torch::Tensor best_reward,
+    torch::Tensor iter_counter, torch::Tensor barrier_buf, torch::Tensor x,
+    torch::Tensor inv_ls, torch::Tensor alpha,
+    std::vector<torch::Tensor> kinv, std::vector<double> amp2,
+    std::vector<double> mean_c, torch::Tensor weights,
+    c10::optional<torch::Tensor> ref, torch::Tensor tr_mask,
+    torch::Tensor out_cont, torch::Tensor k_ws, torch::Tensor mu_ws,
+    torch::Tensor dist_ws, torch::Tensor var_ws, torch::Tensor ms_ws,
+    torch::Tensor score_ws, int64_t n_batches, int64_t batch_size,
+    int64_t pool_size, int64_t it_start, int64_t iterations,
+    double visibility, double gravity, double neg_gravity,
+    double norm_scale, double penalize_factor,
+    double perturbation_lower_bound, double base_perturbation,
+    int64_t seed_suggest, int64_t seed_update, double coef,
+    double tr_radius) {
+  // Every check throws before anything is launched; the state and the
+  // workspaces are written in place and never copied.
+  check_inplace(pool_cont, torch::kFloat32, "pool_cont");
+  check_inplace(rewards, torch::kFloat32, "rewards");
+  check_inplace(perturbations, torch::kFloat32, "perturbations");
+  check_inplace(best_reward, torch::kFloat32, "best_reward");
+  check_inplace(iter_counter, torch::kInt64, "iter_counter");
+  check_inplace(barrier_buf, torch::kInt32, "barrier_buf");
+  check_inplace(out_cont, torch::kFloat32, "out_cont");
+  check_inplace(k_ws, torch::kFloat32, "k_ws");
+  check_inplace(mu_ws, torch::kFloat32, "mu_ws");
+  check_inplace(dist_ws, torch::kFloat32, "dist_ws");
+  check_inplace(var_ws, torch::kFloat32, "var_ws");
+  check_inplace(ms_ws, torch::kFloat32, "ms_ws");
+  check_inplace(score_ws, torch::kFloat32, "score_ws");
+  x = check_f32(x, "x");
+  inv_ls = check_f32(inv_ls, "inv_ls");
+  alpha = check_f32(alpha, "alpha");
+  weights = check_f32(weights, "weights");
+  TORCH_CHECK(tr_mask.is_cuda() && tr_mask.scalar_type() == torch::kUInt8,
+              "tr_mask must be a uint8 GPU tensor");
+  tr_mask = tr_mask.contiguous();
+  TORCH_CHECK(barrier_buf.numel() >= 2, "barrier_buf must be int32 (2,)");
+  const int64_t m64 = (int64_t)kinv.size();
+  TORCH_CHECK(m64 >= 2 && m64 <= 4,
+              "eagle_sweep_mo supports 2 <= M <= 4 metrics, got ", m64);
+  TORCH_CHECK((int64_t)amp2.size() == m64 && (int64_t)mean_c.size() == m64,
+              "amp2 / mean_c must have M = ", m64, " elements");
+  TORCH_CHECK(x.dim() == 2, "x must be (N, Dc)");
+  const int64_t dc64 = x.size(1), n64 = x.size(0);
+  TORCH_CHECK(dc64 >= 1 && dc64 <= 512,
+              "eagle_sweep_mo supports 1 <= Dc <= 512, got ", dc64);
+  // From N = 4096 posterior_mean_std takes its SGEMM quadform and the two
+  // paths would no longer be bit-equal.
+  TORCH_CHECK(n64 >= 1 && n64 < 4096,
+              "eagle_sweep_mo supports 1 <= N < 4096, got ", n64);
+  TORCH_CHECK(pool_size >= 1 && pool_size <= 128,
+              "eagle_sweep_mo supports 1 <= pool <= 128, got ", pool_size);
+  TORCH_CHECK(batch_size >= 1 && batch_size <= 32,
+              "eagle_sweep_mo supports 1 <= batch <= 32, got ", batch_size);
+  TORCH_CHECK(n_batches >= 1 && n_batches * batch_size == pool_size,
+              "pool_size must be n_batches * batch_size, got ", pool_size,
+              " != ", n_batches, " * ", batch_size);
+  TORCH_CHECK(iterations >= 0, "iterations must be >= 0, got ", iterations);
+  // Resident form only: RESIDENT_CAP of eagle_sweep_common.h.
+  TORCH_CHECK(pool_size * dc64 <= 4096,
+              "eagle_sweep_mo keeps the pool in LDS: pool * Dc <= 4096, got ",
+              pool_size * dc64);
+  const int m = (int)m64, dc = (int)dc64, n = (int)n64;
+  TORCH_CHECK(pool_cont.numel() == pool_size * dc,
+              "pool/feature shape mismatch (continuous-only, q=1)");
+  TORCH_CHECK(rewards.numel() == pool_size &&
+              perturbations.numel() == pool_size,
+              "rewards / perturbations must have pool_size = ", pool_size,
+              " elements");
+  TORCH_CHECK(best_reward.numel() >= 1, "best_reward must not be empty");
+  TORCH_CHECK(iter_counter.numel() >= 12,
+              "iter_counter must have >= 12 slots, got ",
+              iter_counter.numel());
+  TORCH_CHECK(inv_ls.dim() == 2 && inv_ls.size(0) == m &&
+              inv_ls.size(1) == dc, "inv_ls must be (", m, ", ", dc, ")");
+  TORCH_CHECK(alpha.dim() == 2 && alpha.size(0) == m && alpha.size(1) == n,
+              "alpha must be (", m, ", ", n, ")");
+  const float* kinv_p[4];
+  float amp2_f[4], mean_c_f[4];
+  for (int i = 0; i < m; ++i) {
+    // Not copied: a contiguous image per call would be M N^2 floats.
+    check_inplace(kinv[i], torch::kFloat32, "kinv");
+    TORCH_CHECK(kinv[i].dim() == 2 && kinv[i].size(0) == n &&
+                kinv[i].size(1) == n, "kinv[", i, "] must be (", n, ", ", n,
+                ")");
+    kinv_p[i] = kinv[i].data_ptr<float>();
+    amp2_f[i] = (float)amp2[i];
+    mean_c_f[i] = (float)mean_c[i];
+  }
+  TORCH_CHECK(weights.dim() == 2 && weights.size(0) >= 1 &&
+              weights.size(1) == m, "weights must be (S >= 1, ", m, ")");
+  const int64_t s64 = weights.size(0);
+  TORCH_CHECK(s64 * m < (int64_t{1} << 31), "weights too large");
+  torch::Tensor ref_t;
+  const float* ref_p = nullptr;
+  if (ref.has_value()) {
+    ref_t = check_f32(*ref, "ref");
+    TORCH_CHECK(ref_t.numel() == m, "ref must have ", m, " elements, got ",
+                ref_t.numel());
+    ref_p = ref_t.data_ptr<float>();
+  }
+  TORCH_CHECK(tr_mask.numel() == dc, "tr_mask must have ", dc,
+              " elements, got ", tr_mask.numel());
+  TORCH_CHECK(out_cont.numel() >= batch_size * dc,
+              "out_cont must hold batch * Dc elements");
+  TORCH_CHECK(k_ws.numel() >= m * batch_size * n,
+              "k_ws must hold M * batch * N elements");
+  TORCH_CHECK(mu_ws.numel() >= m * batch_size,
+              "mu_ws must hold M * batch elements");
+  TORCH_CHECK(dist_ws.numel() >= batch_size && score_ws.numel() >= batch_size,
+              "dist_ws / score_ws must hold batch elements");
+  TORCH_CHECK(ms_ws.numel() >= 2 * m * batch_size,
+              "ms_ws must hold 2 * M * batch elements");
+  const long tiles_n = (n + 63) / 64;
+  TORCH_CHECK(var_ws.numel() >= m * batch_size * (tiles_n * tiles_n + 1),
+              "var_ws must be (M, B, tiles^2 + 1)");
+  // The parity slots (see eagle_sweep.hip): candidates, M mean sums, dist.
+  torch::Tensor slot_ws = torch::empty(
+      {2, batch_size * (dc64 + m + 1)},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  const int ret = launch_eagle_sweep_mo(
+      pool_cont.data_ptr<float>(), rewards.data_ptr<float>(),
+      perturbations.data_ptr<float>(), best_reward.data_ptr<float>(),
+      (unsigned long long*)iter_counter.data_ptr<int64_t>(),
+      (unsigned int*)barrier_buf.data_ptr<int>(), x.data_ptr<float>(),
+      inv_ls.data_ptr<float>(), alpha.data_ptr<float>(), kinv_p, amp2_f,
+      mean_c_f, weights.data_ptr<float>(), ref_p,
+      tr_mask.data_ptr<unsigned char>(), out_cont.data_ptr<float>(),
+      k_ws.data_ptr<float>(), mu_ws.data_ptr<float>(),
+      dist_ws.data_ptr<float>(), var_ws.data_ptr<float>(),
+      ms_ws.data_ptr<float>(), score_ws.data_ptr<float>(),
+      slot_ws.data_ptr<float>(), m, (int)n_batches, (int)batch_size,
+      (int)pool_size, dc, n, (int)s64, (long long)it_start,
+      (long long)iterations, (float)visibility, (float)gravity,
+      (float)neg_gravity, (float)norm_scale, (float)penalize_factor,
+      (float)perturbation_lower_bound, (float)base_perturbation,
+      (unsigned long long)seed_suggest, (unsigned long long)seed_update,
+      (float)coef, (float)tr_radius, current_stream());
+  TORCH_CHECK(ret > 0, "cooperative eagle_sweep_mo launch failed (code ",
+              ret, ")");
+  return ret;
+}
+
 // -- fp64 parity-mode bindings -------------------------------------------------
 
 // Runs the three fp64 scorer kernels on the current stream. `want_score`
@@ -2383,4 +2551,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("eagle_sweep_mixed", &eagle_sweep_mixed,
         "Persistent Eagle sweep megakernel for mixed categorical + "
         "continuous spaces, pool resident in LDS (gfx950)");
+  m.def("eagle_sweep_mo", &eagle_sweep_mo,
+        "Persistent Eagle sweep megakernel for multi-objective studies: M "
+        "Matern GPs, hypervolume scalarisation, one launch (gfx950)");
 }
